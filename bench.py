@@ -9,12 +9,18 @@ Workload (BASELINE.json configs[1]): full MMFN "vec" varia
 XYZI LiDAR sweeps, 64x10x5 lane polylines), random-init weights.  One step = on-GPU ingest
 (crop/normalise, BEV splat) + forward + L1 loss + backward + AdamW — nothing is skipped.
 
-Prints ONE JSON line with the contract fields plus
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line with the contract
+fields (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  --full adds, after the
+timed region,
   roofline      the fp32-MFMA GEMM/implicit-conv kernel family (99 % of the FLOPs): algorithmic
                 FLOPs of its launches / their summed duration, timed with HIP events on the
-                launch stream in extra instrumented steps after the timed region,
+                launch stream in extra instrumented steps (+ the attention kernels timed alone),
+  loss_vs_oracle  the benched batch's loss against the CPU oracle,
   cpu_baseline  the CPU oracle (oracle/, a plain-PyTorch restatement pinned to the reference)
-                timed on this box's host cores on a bounded sample.
+                timed on this box's host cores on a bounded sample,
+  also          the other BASELINE configurations (default one-GPU run only),
+  comm          data-parallel runs: exposed communication, bytes on the wire, lock-step check.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -152,7 +158,7 @@ def also_config(args, name):
     matter, or {"error": ...} - the fp32 line never depends on it."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--steps", str(args.steps), "--warmup", str(args.warmup),
-           "--no-cpu-baseline", "--no-also"]
+           "--full", "--no-cpu-baseline", "--no-also"]
     try:
         out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, cwd=ROOT)
         line = [l for l in out.stdout.decode().splitlines() if l.startswith("{")]
@@ -164,8 +170,46 @@ def also_config(args, name):
     keep = ("metric", "value", "unit", "ms_per_step", "steps", "warmup", "dtype", "loss", "roofline", "loss_vs_oracle")
     rec = {k: rec[k] for k in keep if k in rec}
     rec["config"] = PRESETS[name][0]
-    rec["command"] = "python bench.py --config %s --steps %d --warmup %d" % (name, args.steps, args.warmup)
+    rec["command"] = "python bench.py --config %s --steps %d --warmup %d --full" % (name, args.steps, args.warmup)
     return rec
+
+
+DUMP_SAMPLE = 1 << 22   # elements kept of a larger output: 16 MB in fp32
+DUMP_SEED = 1234
+
+
+def _sample(t, k=DUMP_SAMPLE, seed=DUMP_SEED):
+    """t flattened to fp32 on the host: all of it up to k elements, else the elements at k sorted indices drawn from a fixed
+    seed (the same indices for the same numel in every run)."""
+    t = t.detach().reshape(-1)
+    if t.numel() > k:
+        idx = torch.randint(0, t.numel(), (k,), generator=torch.Generator().manual_seed(seed)).sort().values
+        t = t[idx.to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def dump_outputs(path, net, eng, B, image_only):
+    """What the last timed step computed, as <path>/<name>.npy (fp32, about 50 MB at most):
+      loss, pred          the train step's L1 loss and predicted waypoints [B, pred_len, 2],
+      pooled              image-only workload: the camera branch's pooled features [B, 512],
+      params, grads       the trained parameters after the step's AdamW and their gradients (seeded sample of 4M elements),
+      bn_buffers          the BatchNorm running statistics the step updated (seeded sample beyond 4M elements)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    bufs = eng._bufs_for(B)
+    L = net._layout
+    out = {}
+    if image_only:
+        out["pooled"] = _sample(bufs.get("fused", (B, 512)))
+    else:
+        out["loss"] = _sample(bufs.get("head.loss", (1,)))
+        out["pred"] = bufs.get("head.pred", (B, eng.head.steps, 2)).float().cpu().numpy()
+    out["params"] = _sample(L.params[:L.tail])
+    out["grads"] = _sample(L.grads[:L.tail])
+    out["bn_buffers"] = _sample(L.buffers_flat)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(out)
 
 
 def csrc_digest():
@@ -386,7 +430,15 @@ def main():
                          "`also.rad16`: further bench processes after the fp32 line's timed region)")
     ap.add_argument("--config", default=None, choices=sorted(PRESETS),
                     help="BASELINE.json configuration presets (one flag per config): " + "; ".join("%s = %s" % (k, v[0]) for k, v in sorted(PRESETS.items())))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure and check what the headline does not need: the roofline block, loss_vs_oracle, "
+                         "cpu_baseline, the other BASELINE configurations (`also`) and, data-parallel, the `comm` block (--no-cpu-baseline, "
+                         "--no-oracle-check, --no-attention-roofline, --no-also, --profile-steps and --breakdown trim or extend it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (fp32; rank 0), before anything --full runs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config:   # a preset only fills in the flags the command line left at their defaults
         for k, v in PRESETS[args.config][1].items():
             if getattr(args, k) == ap.get_default(k):
@@ -556,8 +608,10 @@ def main():
         dt = float(t.item())
     ms_per_step = dt / args.steps * 1e3
     value = B * world * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, net, eng, B, image_only)
     comm = None
-    if dp is not None:
+    if dp is not None and args.full:
         in_step = lock_step()
         single_graph = graph is not None and getattr(graph, "single_graph", False)
         if single_graph:
@@ -618,7 +672,7 @@ def main():
     }
     if comm is not None:
         result["comm"] = comm
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel family (fp32 MFMA GEMM / implicit conv)
         prof = ops.GemmProfiler()
         ops.set_gemm_profiler(prof)
@@ -754,6 +808,7 @@ def main():
                                   roofline_frac_algorithmic=result.get("roofline", {}).get("frac_algorithmic"),
                                   attention_fwd_frac=result.get("roofline", {}).get("attention", {}).get("fwd", {}).get("frac"),
                                   attention_bwd_frac=result.get("roofline", {}).get("attention", {}).get("bwd", {}).get("frac"), **scal)
+    if rank == 0:
         print(json.dumps(result))
     if dist is not None:
         dist.barrier()

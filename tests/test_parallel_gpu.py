@@ -220,7 +220,7 @@ def test_bench_launches_its_own_ranks(dtype):  # of gradients per step through g
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(MMFN_BENCH_SINGLE_DEVICE="1", OMP_NUM_THREADS="4")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "0", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "0", "--full", "--no-cpu-baseline",
            "--no-oracle-check", "--profile-steps", "1", "--dtype", dtype, "--grad-dtype", "bf16"]   # the bf16-on-the-wire opt-in
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1200)
     tail = (r.stdout + r.stderr)[-3000:]

@@ -1,7 +1,7 @@
 #!/bin/bash
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
-SHORT="python $R/bench.py --no-graph --single-stream --no-cpu-baseline --no-oracle-check --no-also --steps 1 --warmup 0 --profile-steps 1"
+SHORT="python $R/bench.py --full --no-graph --single-stream --no-cpu-baseline --no-oracle-check --no-also --steps 1 --warmup 0 --profile-steps 1"
 for v in base xcd; do
   if [ $v = xcd ]; then export MMFN_HIP_LIB=$R/mmfn_amd/lib/exp/libmmfn_hip_xcd.so; fi
   rm -rf /tmp/pf_$v

@@ -3,7 +3,7 @@
 # PMC passes) and the resulting TB/s - which streaming kernels sit well below the HBM roofline.  EXTRA: further bench.py flags.
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
-SHORT="python $R/bench.py --no-graph --single-stream --no-cpu-baseline --no-oracle-check --no-also --steps 1 --warmup 0 --profile-steps 1 $EXTRA"
+SHORT="python $R/bench.py --full --no-graph --single-stream --no-cpu-baseline --no-oracle-check --no-also --steps 1 --warmup 0 --profile-steps 1 $EXTRA"
 rm -rf /tmp/kb_t /tmp/kb_f /tmp/kb_w
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kb_t -o t -- $SHORT > /dev/null 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d /tmp/kb_f -o p -- $SHORT > /dev/null 2>&1

@@ -8,9 +8,9 @@ rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 run() {
   name=$1; shift
-  python $R/bench.py --no-cpu-baseline --no-oracle-check "$@" > $OUT/${TAG}_$name.json 2> $OUT/$name.err
+  python $R/bench.py --full --no-cpu-baseline --no-oracle-check "$@" > $OUT/${TAG}_$name.json 2> $OUT/$name.err
   rm -rf $OUT/tr_$name
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/tr_$name -o t -- python $R/bench.py --no-graph --single-stream --no-cpu-baseline --no-oracle-check --steps 2 --warmup 1 --profile-steps 1 "$@" > $OUT/tr_$name.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/tr_$name -o t -- python $R/bench.py --full --no-graph --single-stream --no-cpu-baseline --no-oracle-check --steps 2 --warmup 1 --profile-steps 1 "$@" > $OUT/tr_$name.log 2>&1
   python3 - "$OUT/tr_$name" "$OUT/${TAG}_${name}_kernel_stats.txt" "$name: bench.py $*" <<'PY'
 import csv, glob, sys
 src, dst, title = sys.argv[1:4]

@@ -1,6 +1,7 @@
 mkdir -p gpurun_out/r06
+EV=$_   # the evidence directory just made
 (time timeout 1200 python -m pytest tests -m gpu -x -q) > gpurun_out/r06/gputest.log 2>&1
-timeout 400 python bench.py > gpurun_out/r06/bench.json 2> gpurun_out/r06/bench.err
+timeout 400 python bench.py --full > "$EV/bench.json" 2> "$EV/bench.err"
 bash tools/profile_round.sh r06 > gpurun_out/r06/prof.log 2>&1
 EXTRA="--dtype bf16" bash tools/profile_round.sh r06_bf16 > gpurun_out/r06/prof_bf16.log 2>&1
 cp gpurun_out/prof_r06/summary/* gpurun_out/prof_r06_bf16/summary/* gpurun_out/r06/
