@@ -509,6 +509,24 @@ int mmfn_adamw_f32(float* p, const float* g, float* m, float* v, int64_t n, floa
  * of the flat layout are 16-byte aligned), NULL = all group 0; n must be a multiple of 4; n_groups <= 16. */
 int mmfn_adamw_groups_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of, const float* hyper,
                           int n_groups, const int64_t* step, void* stream);
+/* the same step with every group's grad_scale multiplied by *coef (device memory: the clip coefficient of
+ * mmfn_grad_norm_finalize, so clipping needs no host round trip and stays inside a captured hipGraph) */
+int mmfn_adamw_groups_coef_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of,
+                               const float* hyper, int n_groups, const int64_t* step, const float* coef, void* stream);
+
+/* ---- gradient accumulation and global-norm clipping over the flat gradient buffer ------------------------------ */
+#define MMFN_ACCUM_NONE 0 /* read g only (needs partials) */
+#define MMFN_ACCUM_ADD 1  /* acc += g */
+#define MMFN_ACCUM_FOLD 2 /* g += acc; acc = 0 (idempotent) */
+/* g, acc: n floats, n % 4 == 0, 16-byte aligned (acc unused by NONE), else MMFN_EINVAL.  partials (may be NULL for ADD / FOLD):
+ * mmfn_grad_accum_blocks(n) fp64 slots, one sum of squares of g as it leaves the kernel per workgroup; the grid depends on n
+ * only, so the slots and the summation order are the same on every call. */
+int mmfn_grad_accum_f32(float* g, float* acc, int64_t n, int mode, double* partials, void* stream);
+int mmfn_grad_accum_blocks(int64_t n);
+/* one workgroup: total = the n_partials slots summed in a fixed order (fp64); *norm = *scale * sqrt(total) (fp32);
+ * *coef = min(1, *max_norm / (*norm + 1e-6)) as torch.nn.utils.clip_grad_norm_ (NaN propagates; coef may be NULL). */
+int mmfn_grad_norm_finalize(const double* partials, int n_partials, const float* scale, const float* max_norm, float* norm,
+                            float* coef, void* stream);
 
 /* ---- sensor ingest (dataloader.py:271-308, model_vec.py:33-44,368-381) ------------------------- */
 int mmfn_ingest_rgb_u8(const uint8_t* in, float* out, int B, int H, int W, int crop, void* stream);

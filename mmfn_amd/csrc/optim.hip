@@ -77,10 +77,13 @@ extern "C" int mmfn_adamw_f32(float* p, const float* g, float* m, float* v, int6
 namespace {
 struct GroupScalars { float step_size, decay, bc2_sqrt, beta1, beta2, eps, grad_scale, pad; };
 
+// COEF: every group's grad_scale is multiplied by *coef (the clip_grad_norm_ coefficient, written on the device by
+// mmfn_grad_norm_finalize); COEF = false is the plain grouped step
+template <bool COEF>
 __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                            float* __restrict__ v, int64_t n, const uint8_t* __restrict__ group_of,
                                                            const float* __restrict__ hyper, int n_groups,
-                                                           const int64_t* __restrict__ step) {
+                                                           const int64_t* __restrict__ step, const float* __restrict__ coef) {
   __shared__ GroupScalars gs[MMFN_ADAMW_MAX_GROUPS];
   if ((int)threadIdx.x < n_groups) {
     const float* h = hyper + threadIdx.x * 8;
@@ -90,7 +93,7 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p
     s.step_size = (float)(lr / (1.0 - pow(beta1, t)));
     s.decay = (float)(1.0 - lr * (double)h[4]);
     s.bc2_sqrt = (float)sqrt(1.0 - pow(beta2, t));
-    s.beta1 = h[1]; s.beta2 = h[2]; s.eps = h[3]; s.grad_scale = h[5]; s.pad = 0.f;
+    s.beta1 = h[1]; s.beta2 = h[2]; s.eps = h[3]; s.grad_scale = COEF ? h[5] * *coef : h[5]; s.pad = 0.f;
     gs[threadIdx.x] = s;
   }
   __syncthreads();
@@ -124,8 +127,132 @@ extern "C" int mmfn_adamw_groups_f32(float* p, const float* g, float* m, float* 
       (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15))
     return MMFN_EINVAL;
   const int blocks = (int)std::min<int64_t>(ceil_div64(n / 4, 256), 4096);
-  hipLaunchKernelGGL(adamw_groups_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, group_of, hyper, n_groups,
-                     step);
+  hipLaunchKernelGGL(adamw_groups_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, group_of, hyper,
+                     n_groups, step, (const float*)nullptr);
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mmfn_adamw_groups_coef_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of,
+                                          const float* hyper, int n_groups, const int64_t* step, const float* coef, void* stream) {
+  if (n <= 0) return 0;
+  if (!step || !hyper || !coef || n_groups < 1 || n_groups > MMFN_ADAMW_MAX_GROUPS || (n & 3) ||
+      (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15))
+    return MMFN_EINVAL;
+  const int blocks = (int)std::min<int64_t>(ceil_div64(n / 4, 256), 4096);
+  hipLaunchKernelGGL(adamw_groups_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, group_of, hyper,
+                     n_groups, step, coef);
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- gradient accumulation over the flat buffer + global-norm partials --------------------------------------------------
+// torch's `(loss / k).backward()` k times, then one optimizer step: acc += g per micro-step (ADD), g += acc; acc = 0 at the
+// final one (FOLD: idempotent, a second FOLD adds zeros), the 1 / (k * world) scale and the clip coefficient go into AdamW.
+// Optionally one fp64 sum of squares of the gradient as it LEAVES the kernel per workgroup, into partials[slot + blockIdx.x]:
+// the global norm (clip_grad_norm_) from data already in registers.  The grid depends on n only, so the slots and the summation
+// order are fixed: bitwise the same on every call, eager or replayed.  HBM-bound: ADD / FOLD move 12 B per float, NONE 4 B.
+namespace {
+constexpr int kAccumThreads = 256;
+constexpr int64_t kAccumMaxBlocks = 1024;
+
+int accum_blocks(int64_t n) { return (int)std::min<int64_t>(ceil_div64(n / 4, kAccumThreads), kAccumMaxBlocks); }
+
+__device__ inline double sumsq4(f32x4 v) {
+  return (double)v[0] * v[0] + (double)v[1] * v[1] + (double)v[2] * v[2] + (double)v[3] * v[3];
+}
+
+// fixed-order block sum: 64-lane butterfly, then the four wave sums in wave order
+__device__ inline double block_sum_f64(double s) {
+  __shared__ double wsum[kAccumThreads / 64];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+  __syncthreads();
+  double t = 0.0;
+  if (threadIdx.x == 0)
+    for (int w = 0; w < kAccumThreads / 64; ++w) t += wsum[w];
+  return t;
+}
+
+template <int MODE, bool PARTIALS>
+__global__ __launch_bounds__(kAccumThreads) void grad_accum_kernel(float* __restrict__ g, float* __restrict__ acc, int64_t n4,
+                                                                   double* __restrict__ partials) {
+  double s = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * kAccumThreads + threadIdx.x; i < n4; i += (int64_t)gridDim.x * kAccumThreads) {
+    f32x4 gv = *reinterpret_cast<const f32x4*>(g + i * 4);
+    if (MODE == MMFN_ACCUM_ADD) {
+      f32x4 av = *reinterpret_cast<const f32x4*>(acc + i * 4);
+      *reinterpret_cast<f32x4*>(acc + i * 4) = av + gv;
+    } else if (MODE == MMFN_ACCUM_FOLD) {
+      const f32x4 av = *reinterpret_cast<const f32x4*>(acc + i * 4);
+      gv = gv + av;
+      *reinterpret_cast<f32x4*>(g + i * 4) = gv;
+      *reinterpret_cast<f32x4*>(acc + i * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    if (PARTIALS) s += sumsq4(gv);
+  }
+  if (PARTIALS) {
+    const double t = block_sum_f64(s);
+    if (threadIdx.x == 0) partials[blockIdx.x] = t;
+  }
+}
+
+template <int MODE>
+void launch_accum(float* g, float* acc, int64_t n, double* partials, hipStream_t st) {
+  const int blocks = accum_blocks(n);
+  if (partials)
+    hipLaunchKernelGGL((grad_accum_kernel<MODE, true>), dim3(blocks), dim3(kAccumThreads), 0, st, g, acc, n / 4, partials);
+  else
+    hipLaunchKernelGGL((grad_accum_kernel<MODE, false>), dim3(blocks), dim3(kAccumThreads), 0, st, g, acc, n / 4, partials);
+}
+
+// one workgroup: the partials table summed in a fixed order (strided per thread, then the fixed block sum), norm = scale * sqrt
+__global__ __launch_bounds__(kAccumThreads) void grad_norm_finalize_kernel(const double* __restrict__ partials, int n,
+                                                                           const float* __restrict__ scale,
+                                                                           const float* __restrict__ max_norm,
+                                                                           float* __restrict__ norm, float* __restrict__ coef) {
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += kAccumThreads) s += partials[i];
+  const double t = block_sum_f64(s);
+  if (threadIdx.x == 0) {
+    const float nrm = (float)((double)*scale * sqrt(t));
+    *norm = nrm;
+    if (coef) {
+      // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max=1); a NaN norm propagates into the step
+      const float c = *max_norm / (nrm + 1e-6f);
+      *coef = c > 1.0f ? 1.0f : c;
+    }
+  }
+}
+}  // namespace
+
+extern "C" int mmfn_grad_accum_blocks(int64_t n) { return n > 0 ? accum_blocks(n) : 0; }
+
+extern "C" int mmfn_grad_accum_f32(float* g, float* acc, int64_t n, int mode, double* partials, void* stream) {
+  if (n <= 0) return 0;
+  if (!g || (n & 3) || ((uintptr_t)g & 15) || (mode != MMFN_ACCUM_NONE && (!acc || ((uintptr_t)acc & 15))) ||
+      ((uintptr_t)partials & 7))
+    return MMFN_EINVAL;
+  const hipStream_t st = (hipStream_t)stream;
+  switch (mode) {
+    case MMFN_ACCUM_NONE:
+      if (!partials) return MMFN_EINVAL;   // reads only: without partials it would do nothing
+      launch_accum<MMFN_ACCUM_NONE>(g, acc, n, partials, st);
+      break;
+    case MMFN_ACCUM_ADD: launch_accum<MMFN_ACCUM_ADD>(g, acc, n, partials, st); break;
+    case MMFN_ACCUM_FOLD: launch_accum<MMFN_ACCUM_FOLD>(g, acc, n, partials, st); break;
+    default: return MMFN_EINVAL;
+  }
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mmfn_grad_norm_finalize(const double* partials, int n_partials, const float* scale, const float* max_norm,
+                                       float* norm, float* coef, void* stream) {
+  if (!partials || n_partials < 1 || !scale || !norm || (coef && !max_norm)) return MMFN_EINVAL;
+  hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(kAccumThreads), 0, (hipStream_t)stream, partials, n_partials, scale,
+                     max_norm, norm, coef);
   MMFN_LAUNCH_CHECK();
   return 0;
 }

@@ -1435,6 +1435,11 @@ class Engine(object):
         self.opt_hyper = torch.zeros(16, 8, dtype=torch.float32, device=dev)
         self._hyper_host = None
         self._hyper_pinned, self._hyper_slot = None, 0
+        # gradient accumulation (accumulate_step) and global-norm clipping: allocated on first use only
+        self.grad_acc = None        # fp32 [0, tail): the sum of the pending micro-steps' gradients
+        self.accum_pending = 0      # micro-steps in grad_acc (host count: it picks the 1 / (k * world) of the final step)
+        self._norm = None           # partials table, its slots, and the device (norm, coef) pair
+        self._tiling_checked = False
         self.n_lanes = int(os.environ.get("MMFN_BRANCH_LANES", "3"))
         self.offload_wgrad = True   # transformer weight / bias gradients on the side stream (worth 3.9 ms per step)
 
@@ -1793,7 +1798,7 @@ class Engine(object):
         host = self._hyper_pinned[slot]
         host.zero_()
         for i, r in enumerate(rows):
-            host[i, :6] = torch.tensor(r, dtype=torch.float32)
+            host[i, :len(r)] = torch.tensor(r, dtype=torch.float32)   # (a 7th column: max_norm of a clipped step)
         self.opt_hyper.copy_(host, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
@@ -1810,6 +1815,9 @@ class Engine(object):
         """torch.optim.AdamW step over the trained range of the flat buffer.  `groups`: per-group
         (lr, beta1, beta2, eps, weight_decay) rows (FusedAdamW.hyper_rows()); default one group from the scalars."""
         L = self.layout
+        if self.accum_pending:
+            raise RuntimeError("%d accumulated micro-step(s) are pending: finish them with train_step() or drop them with "
+                               "discard_accumulated() before a direct optimizer_step()" % self.accum_pending)
         groups = self.hyper_rows(lr, betas, eps, weight_decay, grad_scale, groups)
         self.set_hyper(groups)
         self.module.weights_changed()
@@ -1829,12 +1837,167 @@ class Engine(object):
         dp.finish()
         self.optimizer_step(lr=lr, grad_scale=1.0 / dp.world, **adam)
 
-    def train_step(self, inp, gt, lr=1e-4, dp=None, **adam):
+    def train_step(self, inp, gt, lr=1e-4, dp=None, clip_grad_norm=None, **adam):
         """zero-grad (implicit: every gradient is overwritten) + forward + L1 + backward + AdamW
         (phase2_train_net.py:60-110).  `dp` (mmfn_amd.parallel.DataParallel) reduces the gradient
         buckets across ranks while the backward is still running.  `adam` may carry betas / eps /
-        weight_decay.  Returns the device loss scalar."""
+        weight_decay.  Returns the device loss scalar.
+
+        After accumulate_step() calls this is the last micro-step of the group: the pending sum is folded into this
+        backward's gradient and AdamW sees 1 / ((pending + 1) * world) of it.  clip_grad_norm = max_norm: the step is clipped
+        as torch.nn.utils.clip_grad_norm_ over every trained parameter (the norm of the averaged gradient; inf = only measure
+        it), the norm is left in last_grad_norm.  With neither, the launch sequence is the plain step's."""
         ops.rng_advance(self.rng_state)
         _, loss = self.forward(inp, True, gt)
-        self.backward_and_step(dp, lr=lr, **adam)
+        if self.accum_pending == 0 and clip_grad_norm is None:
+            self.backward_and_step(dp, lr=lr, **adam)
+            return loss
+        pending = self.accum_pending
+        self.set_hyper(self.final_rows(lr, pending, dp, clip_grad_norm, **adam))
+        self.backward_groups(ops.ACCUM_FOLD if pending else ops.ACCUM_NONE, dp, clip_grad_norm is not None)
+        self.final_adam(dp, clip_grad_norm is not None, len(self._hyper_host))
         return loss
+
+    # ------------------------------------------------------------------ gradient accumulation / global-norm clipping
+    def accumulate_step(self, inp, gt):
+        """One micro-step of gradient accumulation: RNG advance, forward (BatchNorm running statistics update, as in the torch
+        loop), L1 loss, backward, and acc += gradient per readiness group on the stream that wrote it.  No collective, no AdamW:
+        the next train_step() folds the sum in.  Returns the device loss."""
+        self._accum_buffer()
+        ops.rng_advance(self.rng_state)
+        _, loss = self.forward(inp, True, gt)
+        self.backward_groups(ops.ACCUM_ADD, None, False)
+        self.accum_pending += 1
+        return loss
+
+    def discard_accumulated(self):
+        """Drop the pending micro-steps (acc = 0, count = 0)."""
+        if self.grad_acc is not None:
+            ops.fill(self.grad_acc, 0.0)
+        self.accum_pending = 0
+
+    @property
+    def last_grad_norm(self):
+        """Device tensor [1]: the global gradient norm of the last clipped optimizer step (None before one).  Reading it
+        (.item()) is the only host sync."""
+        return None if self._norm is None else self._norm["out"][0:1]
+
+    def _check_tiling(self):
+        """The per-group passes cover the trained range exactly once only if the readiness groups tile [0, tail) (DataParallel
+        buckets rely on the same): checked once, loudly."""
+        if self._tiling_checked:
+            return
+        L = self.layout
+        r = sorted(L.group_ranges.values())
+        ok = bool(r) and r[0][0] == 0 and r[-1][1] == L.tail and all(a[1] == b[0] for a, b in zip(r, r[1:])) and \
+            all(b % 4 == 0 and e % 4 == 0 for b, e in r)
+        if not ok:
+            raise RuntimeError("the readiness groups of the flat gradient buffer do not tile [0, %d) in 4-float aligned ranges: "
+                               "%s" % (L.tail, r))
+        self._tiling_checked = True
+
+    def _accum_buffer(self):
+        if self.grad_acc is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the gradient accumulator must be allocated before a hipGraph capture")
+            self._check_tiling()
+            self.grad_acc = torch.zeros(self.layout.tail, dtype=torch.float32, device=self.device)
+        return self.grad_acc
+
+    def _norm_state(self):
+        """fp64 partials table: the slots of every readiness group's pass (single GPU), then the slots of one pass over
+        [0, tail) (data parallel: after the reduction); out = device (norm, coef)."""
+        if self._norm is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the gradient-norm tables must be allocated before a hipGraph capture")
+            self._check_tiling()
+            L = self.layout
+            slots, off = {}, 0
+            for key, (b, e) in sorted(L.group_ranges.items(), key=lambda kv: kv[1][0]):
+                n = ops.grad_accum_blocks(e - b)
+                slots[key] = (off, n)
+                off += n
+            full = ops.grad_accum_blocks(L.tail)
+            self._norm = {"partials": torch.zeros(off + full, dtype=torch.float64, device=self.device), "groups": slots,
+                          "n_group_slots": off, "full": (off, full), "out": torch.zeros(2, dtype=torch.float32, device=self.device)}
+        return self._norm
+
+    def group_hooks(self, mode, partials, user=None):
+        """(hook, rest) for one backward: hook(key) runs the accumulation pass `mode` over readiness group `key` (on the
+        stream that reports it, the stream that wrote the group) and then the caller's hook (dp.reduce); rest() passes over
+        the groups the backward never reported, after the join, before the reduction waits for them.  partials: write the
+        group's sum-of-squares slots.  NONE without partials is no pass at all: (user, no-op)."""
+        if mode == ops.ACCUM_NONE and not partials:
+            return user, (lambda: None)
+        L = self.layout
+        acc = self._accum_buffer() if mode != ops.ACCUM_NONE else None
+        nm = self._norm_state() if partials else None
+        done = set()
+
+        def run(key):
+            if key in done:
+                return
+            done.add(key)
+            b, e = L.group_ranges[key]
+            part = None
+            if nm is not None:
+                o, n = nm["groups"][key]
+                part = nm["partials"][o:o + n]
+            ops.grad_accum(L.grads[b:e], None if acc is None else acc[b:e], mode, part)
+
+        def hook(key):
+            run(key)
+            if user is not None:
+                user(key)
+
+        def rest():
+            for key, _ in sorted(L.group_ranges.items(), key=lambda kv: kv[1][0]):
+                run(key)
+
+        return hook, rest
+
+    def backward_groups(self, mode, dp, partials):
+        """Backward of the last training forward with the per-group pass `mode` (accumulate_step: ADD; the final micro-step:
+        FOLD, or NONE with partials for a clipped step without accumulation) in front of dp.reduce.  With dp the norm is taken
+        after the reduction (final_adam), so no group partials here."""
+        hook, rest = self.group_hooks(mode, partials and dp is None, dp.reduce if dp is not None else None)
+        if dp is not None:
+            dp.begin()
+        self.backward(on_ready=hook)
+        rest()
+        if dp is not None:
+            dp.finish()
+
+    def final_rows(self, lr, pending, dp, clip_grad_norm, **adam):
+        """Hyper-parameter rows of the optimizer step that closes an accumulation group of pending + 1 micro-steps:
+        grad_scale = 1 / ((pending + 1) * world), column 6 = max_norm when clipping."""
+        world = dp.world if dp is not None else 1
+        rows = self.hyper_rows(lr=lr, grad_scale=1.0 / ((pending + 1) * world), **adam)
+        if clip_grad_norm is not None:
+            rows = [tuple(r) + (float(clip_grad_norm),) for r in rows]
+        return rows
+
+    def final_adam(self, dp, clip, n_groups):
+        """AdamW after backward_groups, reading the hyper table as set (final_rows); clip: global norm of the scaled
+        gradient (group partials on one GPU, one read-only pass over [0, tail) after the reduction with dp), the coefficient,
+        and the coefficient AdamW.  Resets the pending count."""
+        L = self.layout
+        self.module.weights_changed()
+        ops.step_advance(self.step_count)
+        group_of = self.opt_group_of if n_groups > 1 else None
+        if clip:
+            nm = self._norm_state()
+            if dp is not None:
+                o, n = nm["full"]
+                part = nm["partials"][o:o + n]
+                ops.grad_accum(L.grads[:L.tail], None, ops.ACCUM_NONE, part)
+            else:
+                part = nm["partials"][:nm["n_group_slots"]]
+            out = nm["out"]
+            ops.grad_norm_finalize(part, self.opt_hyper[0, 5:6], self.opt_hyper[0, 6:7], out[0:1], out[1:2])
+            ops.adamw_groups_coef(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self.step_count, self.opt_hyper, n_groups, out[1:2],
+                                  group_of=group_of, n=L.tail)
+        else:
+            ops.adamw_groups(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self.step_count, self.opt_hyper, n_groups,
+                             group_of=group_of, n=L.tail)
+        self.accum_pending = 0

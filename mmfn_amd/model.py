@@ -177,9 +177,15 @@ class MMFN(nn.Module):
         return pred.clone()
 
     # ------------------------------------------------------------------ fused fast path
-    def train_step(self, inp, gt_wp, lr=1e-4, dp=None):
-        """One full training step on device-resident inputs (see engine.Engine.train_step)."""
-        return self._engine_for().train_step(inp, gt_wp, lr=lr, dp=dp)
+    def train_step(self, inp, gt_wp, lr=1e-4, dp=None, clip_grad_norm=None):
+        """One full training step on device-resident inputs (see engine.Engine.train_step): the last micro-step of an
+        accumulation group when accumulate_step() ran before it; clip_grad_norm = max_norm clips as clip_grad_norm_."""
+        return self._engine_for().train_step(inp, gt_wp, lr=lr, dp=dp, clip_grad_norm=clip_grad_norm)
+
+    def accumulate_step(self, inp, gt_wp):
+        """Forward + L1 + backward whose gradient is added to the pending sum; the next train_step() applies it
+        (engine.Engine.accumulate_step)."""
+        return self._engine_for().accumulate_step(inp, gt_wp)
 
     # ------------------------------------------------------------------ PID (model_vec.py:684-726)
     def control_pid(self, waypoints, velocity):

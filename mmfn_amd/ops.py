@@ -1131,6 +1131,35 @@ def adamw_groups(p, g, m, v, step, hyper, n_groups, group_of=None, n=None):
     _call("mmfn_adamw_groups_f32", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(group_of), ptr(hyper), n_groups, ptr(step), stream())
 
 
+def adamw_groups_coef(p, g, m, v, step, hyper, n_groups, coef, group_of=None, n=None):
+    """adamw_groups with every group's grad_scale multiplied by the device scalar `coef` (the clip coefficient)."""
+    n = p.numel() if n is None else n
+    _call("mmfn_adamw_groups_coef_f32", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(group_of), ptr(hyper), n_groups, ptr(step), ptr(coef),
+          stream())
+
+
+ACCUM_NONE, ACCUM_ADD, ACCUM_FOLD = 0, 1, 2   # mirror include/mmfn_hip.h
+
+
+def grad_accum_blocks(n):
+    """fp64 partial slots a grad_accum call over n floats writes (fixed per n)."""
+    return int(lib().mmfn_grad_accum_blocks(int(n)))
+
+
+def grad_accum(g, acc, mode, partials=None):
+    """ADD: acc += g;  FOLD: g += acc, acc = 0;  NONE: read g.  `partials`: a float64 view of grad_accum_blocks(g.numel())
+    slots that receives one sum of squares of g (as it leaves) per workgroup."""
+    if partials is not None and partials.numel() < grad_accum_blocks(g.numel()):
+        raise ValueError("partials view holds %d slots, the pass writes %d" % (partials.numel(), grad_accum_blocks(g.numel())))
+    _call("mmfn_grad_accum_f32", ptr(g), ptr(acc), g.numel(), int(mode), ptr(partials), stream())
+
+
+def grad_norm_finalize(partials, scale, max_norm, norm, coef=None):
+    """norm = scale * sqrt(sum(partials)), coef = min(1, max_norm / (norm + 1e-6)); scale / max_norm / norm / coef: one-element
+    device float tensors (views)."""
+    _call("mmfn_grad_norm_finalize", ptr(partials), partials.numel(), ptr(scale), ptr(max_norm), ptr(norm), ptr(coef), stream())
+
+
 def ingest_rgb_u8(img_u8, out, crop=256):
     B, H, W, _ = img_u8.shape
     _call("mmfn_ingest_rgb_u8", ptr(img_u8), ptr(out), B, H, W, crop, stream())

@@ -254,18 +254,48 @@ class GraphedStep(object):
             RNG advance + forward + loss + head backward + backward of fusion scale 4   -> buckets of stage 0
             backward of scale 3 -> stage 1;  scale 2 -> stage 2;  scale 1 + stems + VectorNet -> stage 3, wait for all
             fused AdamW
-    An eager step is ~2200 Python-issued launches, which makes the host the bottleneck."""
+    An eager step is ~2200 Python-issued launches, which makes the host the bottleneck.
 
-    def __init__(self, engine, dp, inp, gt, lr=1e-4, warm=2, single_graph=None, **adam):
+    variant (gradient accumulation, Engine.accumulate_step): "step" = the plain step above; "micro" = forward, backward and
+    acc += gradient per readiness group, no collective, no AdamW; "final" = the step that closes an accumulation group: the
+    per-group fold (fold=True) in front of each bucket's reduction, optional clipping (clip_grad_norm), AdamW.  k, the size r of a
+    partial group, max_norm and the learning rate only change the device hyper table (set in __call__), never the capture."""
+
+    def __init__(self, engine, dp, inp, gt, lr=1e-4, warm=2, single_graph=None, variant="step", clip_grad_norm=None, fold=True,
+                 **adam):
         from .graphs import Recorder
+        from . import ops
+        if variant not in ("step", "micro", "final"):
+            raise ValueError("variant must be step / micro / final, got %r" % (variant,))
+        if variant == "micro" and dp is not None:
+            raise ValueError("a micro-step issues no collective: capture it without dp")
         self.engine, self.dp = engine, dp
+        self.variant, self.clip, self.fold = variant, clip_grad_norm, bool(fold)
+        self.lr, self.adam = lr, adam
         eng = engine
+        if warm and variant != "step" and eng.accum_pending:
+            raise RuntimeError("warm-up steps would consume the %d pending micro-steps: capture with warm=0" % eng.accum_pending)
         for _ in range(warm):  # size every buffer / scratch lane eagerly before capture
-            eng.train_step(inp, gt, lr=lr, dp=dp, **adam)
+            if variant == "micro":   # no ADD: a warm-up is not a micro-step
+                ops.rng_advance(eng.rng_state)
+                eng.forward(inp, True, gt)
+                eng.backward()
+            else:
+                eng.train_step(inp, gt, lr=lr, dp=dp, clip_grad_norm=clip_grad_norm if variant == "final" else None, **adam)
         torch.cuda.synchronize()
         scale = 1.0 / (dp.world if dp is not None else 1)
         self.scale = scale
-        eng.set_hyper(eng.hyper_rows(lr=lr, grad_scale=scale, **adam))  # the captured AdamW reads them from device memory
+        if variant == "final":
+            mode = ops.ACCUM_FOLD if self.fold else ops.ACCUM_NONE
+            if self.fold:
+                eng._accum_buffer()
+            if clip_grad_norm is not None:
+                eng._norm_state()
+            eng.set_hyper(eng.final_rows(lr, eng.accum_pending, dp, clip_grad_norm, **adam))
+        elif variant == "micro":
+            eng._accum_buffer()
+        else:
+            eng.set_hyper(eng.hyper_rows(lr=lr, grad_scale=scale, **adam))  # the captured AdamW reads them from device memory
         rec = self.recorder = Recorder(eng)
         if dp is not None:
             rec.extra_streams.append(dp.comm_stream)
@@ -278,9 +308,32 @@ class GraphedStep(object):
         self.single_graph = bool(single_graph) or dp is None
 
         def body():
-            from . import ops
             ops.rng_advance(eng.rng_state)
             eng.forward(inp, True, gt)
+            if variant == "micro":
+                eng.backward_groups(ops.ACCUM_ADD, None, False)
+                return
+            if variant == "final":
+                n_groups = len(eng._hyper_host)
+                clip = clip_grad_norm is not None
+                if dp is None or single_graph:
+                    eng.backward_groups(mode, dp, clip)
+                else:
+                    # the folds are enqueued by the hook inside the captured segments, in front of the buckets' reductions at the cuts
+                    tags = []
+                    hook, rest = eng.group_hooks(mode, False, tags.append)
+                    eng.backward_begin(on_ready=hook)
+                    for i in range(4):
+                        eng.backward_scale(3 - i, on_ready=hook)
+                        if i == 3:
+                            rest()
+                        mine, tags[:] = list(tags), []
+                        if i < 3:
+                            rec.cut(lambda mine=mine, i=i: ([dp.reduce(t) for t in mine], dp.on_stage(i)))
+                        else:
+                            rec.cut(lambda mine=mine: ([dp.reduce(t) for t in mine], dp.finish()))
+                eng.final_adam(dp, clip, n_groups)
+                return
             if dp is None or single_graph:
                 # single GPU, or collectives captured on the communication stream (forked from the stream that wrote each
                 # bucket, joined by finish()): no cut, one replay call per step
@@ -298,7 +351,11 @@ class GraphedStep(object):
                         rec.cut(lambda mine=mine: ([dp.reduce(t) for t in mine], dp.finish()))
             eng.optimizer_step(lr=lr, grad_scale=scale, **adam)
 
-        rec.capture(body)
+        pending = eng.accum_pending
+        try:
+            rec.capture(body)
+        finally:
+            eng.accum_pending = pending   # (capturing ran final_adam's host bookkeeping, not a step)
         self.loss = eng._bufs_for(inp["target_point"].shape[0]).get("head.loss", (1,))
 
     def set_hyper(self, lr, **adam):
@@ -306,10 +363,20 @@ class GraphedStep(object):
         self.engine.set_hyper(self.engine.hyper_rows(lr=lr, grad_scale=self.scale, **adam))
 
     def __call__(self):
+        eng = self.engine
+        pending = eng.accum_pending
+        if pending and (self.variant == "step" or (self.variant == "final" and not self.fold)):
+            raise RuntimeError("%d accumulated micro-step(s) are pending: this captured step would drop them" % pending)
+        if self.variant == "final":
+            eng.set_hyper(eng.final_rows(self.lr, pending, self.dp, self.clip, **self.adam))
         if self.dp is not None and not self.single_graph:
             self.dp.begin()   # (single graph: the bucket bookkeeping only ran at capture time)
         self.recorder.replay()
-        self.engine.module.weights_changed()   # the replayed AdamW does not pass through Engine.optimizer_step
+        if self.variant == "micro":
+            eng.accum_pending += 1
+            return self.loss
+        eng.accum_pending = 0
+        eng.module.weights_changed()   # the replayed AdamW does not pass through Engine.optimizer_step
         return self.loss
 
 
@@ -321,14 +388,17 @@ class StaticBatchStep(object):
     (run one eager step of the shape first).  lr / betas / eps / weight decay (per optimizer group) are NOT baked into the
     capture: the AdamW kernel reads them from a device table that __call__ refreshes when they change."""
 
-    def __init__(self, engine, dp, inp, gt, lr, **adam):
+    def __init__(self, engine, dp, inp, gt, lr, variant="step", clip_grad_norm=None, fold=True, **adam):
         self.engine = engine
         self.inp = {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in inp.items()}
         self.gt = gt.clone()
         self.scale = 1.0 / (dp.world if dp is not None else 1)
-        engine.set_hyper(engine.hyper_rows(lr=lr, grad_scale=self.scale, **adam))
+        self.variant = variant
+        if variant == "step":
+            engine.set_hyper(engine.hyper_rows(lr=lr, grad_scale=self.scale, **adam))
         torch.cuda.synchronize()
-        self.seg = GraphedStep(engine, dp, self.inp, self.gt, lr=lr, warm=0, **adam)
+        self.seg = GraphedStep(engine, dp, self.inp, self.gt, lr=lr, warm=0, variant=variant, clip_grad_norm=clip_grad_norm,
+                               fold=fold, **adam)
         self.loss = self.seg.loss
         self.run = self.seg
 
@@ -340,7 +410,10 @@ class StaticBatchStep(object):
 
     def __call__(self, inp, gt, lr=None, **adam):
         if lr is not None:
-            self.engine.set_hyper(self.engine.hyper_rows(lr=lr, grad_scale=self.scale, **adam))
+            if self.variant == "step":
+                self.engine.set_hyper(self.engine.hyper_rows(lr=lr, grad_scale=self.scale, **adam))
+            else:   # (the final variant sets its rows at replay: the scale depends on the pending micro-steps)
+                self.seg.lr, self.seg.adam = lr, adam
         for k, v in inp.items():
             if isinstance(v, torch.Tensor):
                 self.inp[k].copy_(v, non_blocking=True)

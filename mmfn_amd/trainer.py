@@ -55,21 +55,51 @@ class Trainer(object):
 
     # ------------------------------------------------------------------ one epoch of training
     def train(self, model, dataloader_train, config, optimizer, dp=None, fused=True, log_every=50, on_log=None, graph=True,
-              lane_bucket=16):
+              lane_bucket=16, accum_steps=1, clip_grad_norm=None):
         """One epoch.  graph=True (fused path): the second batch of a given shape captures the step into hipGraphs over
         static input buffers and every later batch of that shape only copies its inputs and replays (the first one runs
         eagerly and sizes the buffers); lane sets are zero-padded to a multiple of `lane_bucket` lanes so that ragged
         batches fall into few shapes (padded lanes are masked by lane_num: outputs are unchanged, parameter gradients to
-        the last ulp of their row sums)."""
+        the last ulp of their row sums).
+
+        accum_steps = k: gradient accumulation, one optimizer step per k consecutive batches on the mean of their
+        gradients (each batch's own mean L1 loss, BatchNorm statistics per batch); the epoch's last, partial group of r < k
+        batches is stepped at the end of the epoch with 1 / r, so no gradient crosses an epoch (or checkpoint) boundary.
+        cur_iter keeps counting batches.  Under data parallelism every rank must pass the same accum_steps (a
+        DistributedSampler gives every rank the same number of batches), and the gradient all-reduce runs once per group.
+        clip_grad_norm = max_norm: torch.nn.utils.clip_grad_norm_ over all trained parameters before each optimizer step
+        (inf: only measure); on_log then also gets "grad_norm", the last optimizer step's global norm.  Each variant of the
+        step (micro-step, group-closing step) is a captured shape of its own, bounded by max_captured_shapes."""
+        accum_steps = int(accum_steps)
+        if accum_steps < 1:
+            raise ValueError("accum_steps must be >= 1, got %d" % accum_steps)
+        accumulating = accum_steps > 1 or clip_grad_norm is not None
+        if accumulating and not fused:
+            raise NotImplementedError("accum_steps / clip_grad_norm are options of the fused step (fused=True)")
         model.train()
         eng = model._engine_for()
+        if accumulating and eng.accum_pending:
+            raise RuntimeError("%d micro-step(s) are pending from outside this epoch" % eng.accum_pending)
+        in_group = 0
         if not hasattr(self, "_static_steps"):
             self._static_steps = {}      # input-shape signature -> "seen" | "eager" | StaticBatchStep, in LRU order
         total = torch.zeros(1, dtype=torch.float32, device=model._layout.device)
         window = torch.zeros_like(total)
         num_batches = 0
-        for args, gt in D.DevicePrefetcher(dataloader_train, self.device, config, variant=model.variant):
-            if fused:
+        batches = D.DevicePrefetcher(dataloader_train, self.device, config, variant=model.variant)
+        # (accumulating: one batch of look-ahead tells the epoch's last batch, which closes the partial group)
+        for (args, gt), last in (_with_last(batches) if accumulating else ((b, False) for b in batches)):
+            if fused and accumulating:
+                inp = args if isinstance(args, dict) else model._pack(*args)
+                adam = dict(groups=_hyper_rows(optimizer))
+                lr = optimizer.param_groups[0]["lr"]
+                inp = _bucket_lanes(inp, lane_bucket)
+                in_group += 1
+                final = in_group == accum_steps or last
+                loss = self._accum_call(eng, dp, inp, gt, lr, adam, final, accum_steps > 1, clip_grad_norm, graph)
+                if final:
+                    in_group = 0
+            elif fused:
                 inp = args if isinstance(args, dict) else model._pack(*args)  # raw-frame batches are engine inputs already
                 # per-group (lr, beta1, beta2, eps, weight_decay): read every step, so an LR scheduler just works - they go
                 # to the device table the AdamW kernel reads, captured graphs stay valid
@@ -112,11 +142,43 @@ class Trainer(object):
             self.cur_iter += 1
             num_batches += 1
             if on_log is not None and num_batches % log_every == 0:
-                on_log({"loss": float(window.item()) / log_every, "iter": self.cur_iter})
+                rec = {"loss": float(window.item()) / log_every, "iter": self.cur_iter}
+                if clip_grad_norm is not None:   # (None until the first optimizer step of the run)
+                    rec["grad_norm"] = None if eng.last_grad_norm is None else float(eng.last_grad_norm.item())
+                on_log(rec)
                 window.zero_()
         self.train_loss.append(float(total.item()) / max(num_batches, 1))
         self.cur_epoch += 1
         return self.train_loss[-1]
+
+    def _accum_call(self, eng, dp, inp, gt, lr, adam, final, fold, clip, graph):
+        """One batch of an accumulation group: a micro-step, or (final) the step that closes the group.  graph=True: per
+        (shape, variant) the first call runs eagerly, the second captures (parallel.StaticBatchStep), later ones replay."""
+        if not graph:
+            return eng.train_step(inp, gt, lr=lr, dp=dp, clip_grad_norm=clip, **adam) if final else eng.accumulate_step(inp, gt)
+        variant = "final" if final else "micro"
+        sig = (StaticBatchStep.signature(inp, gt), variant, fold, clip is not None)
+        state = self._static_steps.pop(sig, None)
+        if state is not None and state != "eager":
+            if state == "seen":
+                try:
+                    state = StaticBatchStep(eng, None if variant == "micro" else dp, inp, gt, lr, variant=variant, clip_grad_norm=clip,
+                                            fold=fold, **adam)
+                except RuntimeError as exc:
+                    import warnings
+                    warnings.warn("hipGraph capture of the %s step failed (%s); continuing with eager launches" % (variant, exc))
+                    torch.cuda.synchronize()
+                    state = "eager"
+        if state is None or state == "eager":
+            loss = eng.train_step(inp, gt, lr=lr, dp=dp, clip_grad_norm=clip, **adam) if final else eng.accumulate_step(inp, gt)
+            state = state or "seen"
+        else:
+            state.seg.clip = clip   # max_norm lives in the hyper table: a new value is no new capture
+            loss = state(inp, gt, lr=lr, **adam)
+        self._static_steps[sig] = state
+        while len(self._static_steps) > self.max_captured_shapes:
+            _evict_lru(self._static_steps)
+        return loss
 
     # ------------------------------------------------------------------ validation (no grad, eval-mode BN, no dropout)
     def validate(self, model, dataloader_val, config, graph=True, lane_bucket=16):
@@ -226,6 +288,19 @@ class Trainer(object):
         return True
 
 
+def _with_last(it):
+    """(item, is_last) pairs: one item of look-ahead (the prefetcher has it in flight already)."""
+    it = iter(it)
+    try:
+        prev = next(it)
+    except StopIteration:
+        return
+    for item in it:
+        yield prev, False
+        prev = item
+    yield prev, True
+
+
 def _bucket_lanes(inp, bucket):
     lane = inp.get("lane")
     if lane is None or bucket <= 1 or lane.shape[1] % bucket == 0:
@@ -297,12 +372,14 @@ def _plain_state_dict(model):
 
 
 def fit(model, optimizer, train_loader, val_loader, config, logdir, epochs, val_every=1, save_every=1, dp=None, rank=0,
-        on_log=None, dist=None):
+        on_log=None, dist=None, accum_steps=1, clip_grad_norm=None):
     """The epoch loop of phase2_train_net.py:307-322: train every epoch; rank 0 validates every `val_every`
     epochs and saves every `save_every`.  Data parallel: pass `dp` (a parallel.DataParallel), or just the initialised
     torch.distributed module as `dist` - the transport is then chosen by parallel.connect: the C-ABI RCCL communicator when it
     passes its self-test on every rank (the whole step, gradient all-reduces included, replays as ONE hipGraph per batch shape),
-    else torch.distributed (four graphs per step, buckets in between); a capture that fails continues eagerly."""
+    else torch.distributed (four graphs per step, buckets in between); a capture that fails continues eagerly.
+    accum_steps / clip_grad_norm: gradient accumulation and global-norm clipping (Trainer.train; the same accum_steps on
+    every rank)."""
     if dp is None and dist is not None and dist.get_world_size() > 1:
         from .parallel import connect
         dp, _ = connect(model, dist)
@@ -317,7 +394,8 @@ def fit(model, optimizer, train_loader, val_loader, config, logdir, epochs, val_
         sampler = getattr(train_loader, "sampler", None)
         if hasattr(sampler, "set_epoch"):
             sampler.set_epoch(epoch)
-        trainer.train(model, train_loader, config, optimizer, dp=dp, on_log=on_log if rank == 0 else None)
+        trainer.train(model, train_loader, config, optimizer, dp=dp, on_log=on_log if rank == 0 else None, accum_steps=accum_steps,
+                      clip_grad_norm=clip_grad_norm)
         if epoch % val_every == 0 and rank == 0 and val_loader is not None:
             trainer.validate(model, val_loader, config)
             if epoch % save_every == 0:
