@@ -72,7 +72,7 @@ class GptBlockDesc(ctypes.Structure):
 class Conv16HaloDesc(ctypes.Structure):
     """mmfn_conv16_halo_desc (include/mmfn_hip.h): the LDS-resident-patch 3x3 convolution of the bf16 mode."""
     _PTRS = ("x", "w", "out", "stats", "out_res", "bn2_y", "bn2_x", "bn2_mean", "bn2_rstd", "p_mean", "p_rstd", "p_weight", "p_bias",
-             "p_means", "p_res", "p_y", "p_x", "a_out", "ge_out")
+             "p_res", "a_out")
     _fields_ = [(n, _vp) for n in _PTRS] + [(n, _i32) for n in ("B", "H", "W", "K", "N", "pro", "relu", "flip", "tile", "stages",
                                                                 "stats_mode")]
 

@@ -1,17 +1,17 @@
 // 3x3 stride-1 convolution of the bf16 training mode with the input patch of a pixel tile resident in LDS (bf16 operands,
 // v_mfma_f32_32x32x16_bf16, fp32 accumulation).  Replaces, for the torchvision BasicBlock convolutions of the three ResNet trunks
 // (model_vec.py:509-521,539-593) under torch.autocast-style arithmetic, the cuDNN convolution forward / backward-data dispatch
-// TOGETHER with the elementwise pass that produces its input: native_batch_norm's apply (+ skip + ReLU) in the forward, the
-// BatchNorm backward's apply in the data gradient.
+// TOGETHER with the elementwise pass that produces its input: native_batch_norm's apply (+ skip + ReLU) in the forward; the data
+// gradient runs the same kernel with the taps reversed and no prologue function.
 //
 // Why not the implicit GEMM of gemm_bf16.hip: that kernel gathers every input pixel nine times (once per tap) from L2 into LDS -
 // the bf16 trunk convolutions were L2-bound (9-12 TB/s of L2 -> LDS traffic), and because the operands travel global -> LDS
 // directly nothing can be applied to them on the way, so each ConvBN needed the apply launch and a round trip of the activation.
 // Here a block owns BM = 64 / 128 output pixels (TI images x TH rows x TW columns) and BN output channels:
 //   1. prologue: the (TH + 2) x (TW + 2) halo patch, ALL contraction channels, goes global -> registers -> LDS once.  On the way
-//      the producer's elementwise function is applied (PRO 1: y = [relu](bn(co) [+ res]); PRO 2: dco = BatchNorm backward of
-//      g), pixels outside the image become zeros of the APPLIED tensor, and the block of column tile 0 writes the applied
-//      values of the pixels it owns to HBM (the activation the skip connection / the weight gradient / the backward mask read);
+//      the producer's elementwise function is applied (PRO 1: y = [relu](bn(co) [+ res])), pixels outside the image become
+//      zeros of the APPLIED tensor, and the block of column tile 0 writes the applied values of the pixels it owns to HBM (the
+//      activation the skip connection / the weight gradient / the backward mask read);
 //   2. main loop over (tap, 64-channel chunk) in the k order of the implicit GEMM (so the accumulation sequence, and with it
 //      every output bit, equals the gather kernel's on equal inputs): the A fragments are ds_read_b128s of the resident patch
 //      at the tap's row offset, only the filter tiles stream through an LDS ring (global_load_lds, counted vmcnt waits);
@@ -132,27 +132,18 @@ __global__ __launch_bounds__(NT) void conv16_halo_kernel(const mmfn_conv16_halo_
     int pi = row / per_img, rem = row - pi * per_img;
     int py = rem / g.TW2, px = rem - py * g.TW2;
     const int dy = RPI / g.TW2, dx = RPI - dy * g.TW2;
-    float ca[8], cb[8], cc[8], cd[8], ce[8];
+    float ca[8], cb[8];
     if (PRO == 1) {         // y = fma(x, alpha, beta) [+ res] [relu]   (bn_apply_kernel's spelling)
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         ca[e] = mmfn_bn_alpha(d.p_weight[c0 + e], d.p_rstd[c0 + e]);
         cb[e] = mmfn_bn_beta(d.p_bias[c0 + e], d.p_mean[c0 + e], ca[e]);
       }
-    } else if (PRO == 2) {  // dco = (ge - m1 - xhat * m2) * (w * rstd)   (bn_bwd_apply_kernel)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        ca[e] = d.p_rstd[c0 + e];
-        cb[e] = d.p_mean[c0 + e];
-        cc[e] = d.p_means[c0 + e];
-        cd[e] = d.p_means[K + c0 + e];
-        ce[e] = d.p_weight[c0 + e] * ca[e];
-      }
     }
     const bool writer = n0 == 0;
     constexpr int U = 4;
     for (int r0 = 0; r0 < g.PR; r0 += U * RPI) {
-      uint4 v0[U], v1[U], v2[U];
+      uint4 v0[U], v1[U];
       ptrdiff_t src[U];
       int lrow[U];
       bool own[U];
@@ -174,14 +165,9 @@ __global__ __launch_bounds__(NT) void conv16_halo_kernel(const mmfn_conv16_halo_
       for (int u = 0; u < U; ++u) {
         v0[u] = make_uint4(0, 0, 0, 0);
         v1[u] = v0[u];
-        v2[u] = v0[u];
         if (src[u] >= 0) {
           v0[u] = *reinterpret_cast<const uint4*>(X + src[u]);
           if (PRO == 1 && d.p_res) v1[u] = *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned short*>(d.p_res) + src[u]);
-          if (PRO == 2) {
-            v1[u] = *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned short*>(d.p_x) + src[u]);
-            if (d.p_y) v2[u] = *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned short*>(d.p_y) + src[u]);
-          }
         }
       }
 #pragma unroll
@@ -204,27 +190,6 @@ __global__ __launch_bounds__(NT) void conv16_halo_kernel(const mmfn_conv16_halo_
           }
           o = pack8(f);
           if (writer && own[u] && d.a_out) *reinterpret_cast<uint4*>(reinterpret_cast<unsigned short*>(d.a_out) + src[u]) = o;
-        } else if (PRO == 2 && src[u] >= 0) {
-          const Row8 gv = unpack8(v0[u]), xv = unpack8(v1[u]);
-          float ge[8], f[8];
-          if (d.p_y) {
-            const Row8 yv = unpack8(v2[u]);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) ge[e] = yv.v[e] > 0.0f ? gv.v[e] : 0.0f;
-          } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) ge[e] = gv.v[e];
-          }
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const float xh = (xv.v[e] - cb[e]) * ca[e];
-            f[e] = (ge[e] - cc[e] - xh * cd[e]) * ce[e];
-          }
-          o = pack8(f);
-          if (writer && own[u]) {
-            if (d.a_out) *reinterpret_cast<uint4*>(reinterpret_cast<unsigned short*>(d.a_out) + src[u]) = o;
-            if (d.ge_out) *reinterpret_cast<uint4*>(reinterpret_cast<unsigned short*>(d.ge_out) + src[u]) = pack8(ge);
-          }
         }
         const int sw = narrow ? ((lrow[u] >> 1) & 7) : (lrow[u] & 15);
         *reinterpret_cast<uint4*>(smem + lrow[u] * pitch + ((q ^ sw) << 4)) = o;
@@ -510,19 +475,15 @@ extern "C" int mmfn_conv3x3_halo_bf16_stats_rows(const mmfn_conv16_halo_desc* d)
 extern "C" int mmfn_conv3x3_halo_bf16(const mmfn_conv16_halo_desc* dp, void* stream) {
   if (!dp) return MMFN_EINVAL;
   const mmfn_conv16_halo_desc& d = *dp;
-  if (!d.x || !d.w || !d.out || d.pro < 0 || d.pro > 2) return MMFN_EINVAL;
+  if (!d.x || !d.w || !d.out || d.pro < 0 || d.pro > 1) return MMFN_EINVAL;
   if (d.pro == 1 && (!d.p_mean || !d.p_rstd || !d.p_weight || !d.p_bias)) return MMFN_EINVAL;
-  if (d.pro == 2 && (!d.p_mean || !d.p_rstd || !d.p_weight || !d.p_means || !d.p_x)) return MMFN_EINVAL;
   if (d.stats && d.stats_mode != 0 && d.stats_mode != 2) return MMFN_EINVAL;
   if (d.stats && d.stats_mode == 2 && (!d.bn2_x || !d.bn2_mean || !d.bn2_rstd)) return MMFN_EINVAL;
   int tile, nsw;
   HaloGeom g;
   if (!pick_config(d, &tile, &nsw, &g)) return MMFN_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  int rc;
-  if (d.pro == 0) rc = launch_tile<0>(d, g, tile, nsw, s);
-  else if (d.pro == 1) rc = launch_tile<1>(d, g, tile, nsw, s);
-  else rc = launch_tile<2>(d, g, tile, nsw, s);
+  const int rc = d.pro == 0 ? launch_tile<0>(d, g, tile, nsw, s) : launch_tile<1>(d, g, tile, nsw, s);
   if (rc) return rc;
   MMFN_LAUNCH_CHECK();
   return 0;

@@ -126,7 +126,6 @@ class Ctx(object):
 
 
 # ----------------------------------------------------------------------------- conv + BN
-FUSE_BN_BWD_REDUCE = True   # see ConvBN.bwd16 (bf16 mode)
 # fp32: a BatchNorm apply (+ residual + ReLU) whose consumer is an F(4x4) Winograd convolution runs inside that convolution's input
 # transform (PendingBN).  A/B switch; 0 = every BatchNorm apply is its own launch (the round-3 step).
 LAZY_BN_APPLY = os.environ.get("MMFN_LAZY_BN", "1") == "1"
@@ -136,12 +135,9 @@ LAZY_BN_APPLY = os.environ.get("MMFN_LAZY_BN", "1") == "1"
 # mmfn_conv3x3_halo_bf16 (csrc/conv16_halo.hip), which applies the producer's BatchNorm (+ skip + ReLU) while it stages its halo
 # patch and writes the activation for the pixels it owns.  Measured per shape (tools/halo_bench.py, B = 32): 64 / 128 contraction
 # channels 1.3-1.4 x the apply + implicit-GEMM pair; 256 / 512 channels are bound by the filter stream per 64-pixel tile and stay on
-# the implicit GEMM (MMFN_HALO_MAX_K).  MMFN_HALO_CONV=0 restores round 5's launch sequence.
-HALO_MAX_K = int(os.environ.get("MMFN_HALO_MAX_K", "128"))
-# backward: 0 = implicit-GEMM data gradients (round 5), 1 = the halo kernel as the data gradient, 2 = also the BatchNorm backward's
-# elementwise pass in its loader (ConvBN.bwd16).  Same-box A/B (vec B = 32, medians of 3 x 100 steps): 16.35 / 16.09 / 16.19 ms - the
-# fused loader reads three tensors per patch element and makes the weight gradient wait for the data gradient: 1 is the default.
-HALO_BWD = int(os.environ.get("MMFN_HALO_BWD", "1"))
+# the implicit GEMM (256 channels on the halo kernel measured slower: 16.59 vs 16.25 ms per step).  The same kernel is the data
+# gradient of those layers (ConvBN.bwd16).
+HALO_MAX_K = 128
 
 
 class PendingBN(object):
@@ -204,7 +200,7 @@ class ConvBN(object):
 
     # ---- the 7x7 stems (3 / 2 input channels) as explicit im2col + plain GEMM (csrc/misc.hip: mmfn_im2col_small)
     def is_stem(self):
-        return self.w.shape[3] <= 4 and ops.STEM_IM2COL
+        return self.w.shape[3] <= 4
 
     def stem_conv(self, ctx, x, co, stats=None, w=None, bias=None, relu=False):
         """co [B,OH,OW,Cout] = conv(x) through the patch matrix, which is kept for the weight gradient (stem_wgrad).
@@ -244,12 +240,13 @@ class ConvBN(object):
         channels then runs as mmfn_conv3x3_halo_bf16 and applies that BatchNorm (+ skip + ReLU) in its loader; lazy: return this
         layer's own PendingBN instead of launching the apply."""
         from . import ops16
-        # the LDS-resident-patch kernel (3x3 stride 1): takes the producer's PendingBN as it is and applies it in its loader
-        halo = x.dtype == torch.bfloat16 and x.shape[-1] <= HALO_MAX_K and ops16.halo_ok(tuple(x.shape), tuple(self.w.shape), self.stride, self.pad) > 0
+        # the LDS-resident-patch kernel (3x3 stride 1): takes the producer's PendingBN as it is and applies it in its loader (pro 1)
+        pend = x if isinstance(x, PendingBN) and x.y is None and LAZY_BN_APPLY and not ctx.folded else None
+        halo = x.dtype == torch.bfloat16 and x.shape[-1] <= HALO_MAX_K and \
+            ops16.halo_ok(tuple(x.shape), tuple(self.w.shape), self.stride, self.pad, pro=1 if pend is not None else 0) > 0
         x_bn = None
         if isinstance(x, PendingBN):
-            if halo and x.y is None and LAZY_BN_APPLY and not ctx.folded:
-                pend = x
+            if halo and pend is not None:
                 x_bn = pend.consume(ctx, True)    # (res, mean, rstd, weight, bias, relu, y_out): y is written by this convolution
                 xin, x = pend.co, pend.y
             else:
@@ -311,7 +308,7 @@ class ConvBN(object):
             ops.bn_eval_prepare(bn.running_mean, bn.running_var, mean, rstd, bn.eps)
         self.saved = [x, co, None, mean, rstd, relu]   # saved[2]: the activation, written by PendingBN.tensor() or by the consumer's loader
         pend = PendingBN(self, co, res, relu)
-        if lazy and LAZY_BN_APPLY and HALO_MAX_K > 0:
+        if lazy and LAZY_BN_APPLY:
             return pend
         return pend.tensor(ctx)
 
@@ -325,18 +322,7 @@ class ConvBN(object):
         dco = ctx.bufs.get(self.name + ".dconv", co.shape, co.dtype)
         ymask = (y if mask_y is None else mask_y).view(M, self.cout) if relu else None
         pre, self._pre = getattr(self, "_pre", None), None
-        # data gradient through the LDS-resident-patch kernel (3x3 stride 1, contraction = this layer's output channels); with the
-        # reductions already emitted by the layer above (`pre`) the BatchNorm backward's elementwise pass runs in ITS loader: the
-        # chain is finalize -> data gradient (which writes dco for the weight gradient) instead of finalize -> apply -> data gradient
-        halo_dg = need_dx and HALO_BWD >= 1 and x.dtype == torch.bfloat16 and co.dtype == torch.bfloat16 and self.cout <= HALO_MAX_K and \
-            ops16.halo_ok(tuple(co.shape), tuple(self.w16t.shape), self.stride, self.pad) > 0
-        fuse = halo_dg and HALO_BWD >= 2 and pre is not None and mask_y is None
-        bn_bwd_arg = None
-        if fuse:
-            means = ctx.bufs.get(self.name + ".bnmeans", (2, self.cout))
-            ops16.bn_bwd_finalize(pre[0], pre[1], M, self.cout, self.g_bn_w, self.g_bn_b, means)
-            bn_bwd_arg = (mean, rstd, self.bn_w, means, y if relu else None, co, dco, ge_out)
-        elif pre is not None and mask_y is None and co.dtype == torch.bfloat16:
+        if pre is not None and mask_y is None and co.dtype == torch.bfloat16:
             ops16.bn_bwd_partials(pre[0], pre[1], g.view(M, self.cout), ymask, co.view(M, self.cout), mean, rstd, self.bn_w,
                                   dco.view(M, self.cout), self.g_bn_w, self.g_bn_b,
                                   ge_out=None if ge_out is None else ge_out.view(M, self.cout))
@@ -349,25 +335,24 @@ class ConvBN(object):
             else:
                 ops.conv2d_wgrad(dco, x, tuple(self.w.shape), self.stride, self.pad, out=self.gw)
             return None
-        if not fuse:
-            ops16.conv2d_wgrad(dco, x, tuple(self.w.shape), self.stride, self.pad, self.gw)
+        ops16.conv2d_wgrad(dco, x, tuple(self.w.shape), self.stride, self.pad, self.gw)
         if not need_dx:
             return None
         dx = ctx.bufs.get(self.name + ".dx", x.shape, ctx.adt)
         cin = x.shape[-1]
         extra = {}
-        if emit is not None and FUSE_BN_BWD_REDUCE and emit.saved[1].dtype == torch.bfloat16:
+        if emit is not None and emit.saved[1].dtype == torch.bfloat16:
             ex, eco, ey, emean, erstd, erelu = emit.saved
             Mx = x.shape[0] * x.shape[1] * x.shape[2]
             part = ctx.bufs.get(emit.name + ".bnpart", (ops16.max_stats_rows(Mx), 2, cin), torch.float64)
             extra = dict(stats=part, stats_mode=2, bn=(ey if erelu else None, eco, emean, erstd))
-        if halo_dg:
-            rows = ops16.conv3x3_halo(g if fuse else dco, self.w16t, dx, flip=True, out_res=dx_res, stats=extra.get("stats"), stats_mode=2,
-                                      bn2=extra.get("bn"), bn_bwd=bn_bwd_arg)
+        # data gradient through the LDS-resident-patch kernel (3x3 stride 1, contraction = this layer's output channels)
+        if co.dtype == torch.bfloat16 and self.cout <= HALO_MAX_K and \
+                ops16.halo_ok(tuple(co.shape), tuple(self.w16t.shape), self.stride, self.pad) > 0:
+            rows = ops16.conv3x3_halo(dco, self.w16t, dx, flip=True, out_res=dx_res, stats=extra.get("stats"), stats_mode=2,
+                                      bn2=extra.get("bn"))
             if "stats" in extra:
                 emit._pre = (extra["stats"], rows)
-            if fuse:   # dco exists only now: the loader of the data gradient wrote it
-                ops16.conv2d_wgrad(dco, x, tuple(self.w.shape), self.stride, self.pad, self.gw)
             return dx
         if dx_res is not None:
             extra.update(res=dx_res.view(-1, cin), ldr=cin)
@@ -587,9 +572,6 @@ class Linear(object):
         self.w16 = self.w16t = None   # bf16 shadows [out, in] / [in, out] (Engine._build_shadows, bf16 mode)
 
 
-DEFER_LN_REDUCTIONS = True   # see LayerNorm.bwd
-
-
 class LayerNorm(object):
     def __init__(self, name, layout, prefix):
         self.name = name
@@ -610,7 +592,7 @@ class LayerNorm(object):
         x, mean, rstd, act = self.saved
         dx = ctx.bufs.get(self.name + ".dx", x.shape, x.dtype) if out is None else out
         rng = ctx.rng_state if dropped is not None else None
-        if (defer is True or isinstance(defer, list)) and ctx.side is not None and DEFER_LN_REDUCTIONS:
+        if (defer is True or isinstance(defer, list)) and ctx.side is not None:
             # the chain only needs dx: the reduction of the per-block partial rows into the weight / bias gradients (and the
             # consuming Linear's bias gradient) goes to the side stream, like the weight-gradient GEMMs (0.8 ms of ~11 us
             # launches per step off the transformers' dependent chain); own partial buffer, it must outlive this call
@@ -633,13 +615,10 @@ class LayerNorm(object):
 
 
 # ----------------------------------------------------------------------------- GPT fusion transformer
-# fp32 path: ln1 -> key/query/value and ln2 -> mlp.0 as ONE launch each (MMFN_EPI_LN_FOLD: the LayerNorm folded into the GEMM,
-# include/mmfn_hip.h mmfn_gemm_desc.ln_c1); in a training step the normalised tensor that only the weight gradient needs is
-# recomputed on the side stream in the backward.  MMFN_LN_FOLD = "eval" (default): eval-mode forwards only - validation and the
-# batch-1 closed-loop tick, where 64 launches less on a dependent chain of ~330 are worth 4 % (4.05 vs 4.22 ms per tick);
-# "1": training too - measured SLOWER there (32.01 vs 31.74 ms per step, DESIGN.md section 5: the folded GEMMs cost what the
-# LayerNorm launches saved, and the recomputation competes with the backward's side work); "0": never.
-LN_FOLD = os.environ.get("MMFN_LN_FOLD", "eval")
+# fp32 eval-mode forwards: ln1 -> key/query/value and ln2 -> mlp.0 as ONE launch each (MMFN_EPI_LN_FOLD: the LayerNorm folded into
+# the GEMM, include/mmfn_hip.h mmfn_gemm_desc.ln_c1) - validation and the batch-1 closed-loop tick, where 64 launches less on a
+# dependent chain of ~330 are worth 4 % (4.05 vs 4.22 ms per tick).  Such a forward keeps no normalised tensor, so no backward can
+# follow it.  Folding in training steps too was measured slower (32.01 vs 31.74 ms per step, tools/experiments/NOTES.md) and removed.
 # Side work of the transformers up to this width alternates between TWO side streams (GPT._offload_side): their blocks are
 # launch-bound on the chain AND on the side stream (8 against ~14 launches of 5-8 us per block), so the join at the end of the
 # transformer waited for the side stream.  Measured (3 interleaved runs each): bf16 step 17.55 -> 17.16 ms, fp32 31.62 -> 31.37;
@@ -648,8 +627,7 @@ LN_FOLD = os.environ.get("MMFN_LN_FOLD", "eval")
 SIDE_SPLIT_MAX_C = 256
 # The narrow transformers (n_embd 64 / 128, fp32): a block is 2 forward launches (ln1 + q/k/v + attention per (sample, head, half);
 # proj + ln2 + mlp per 32-row block) and 3 backward launches (dQ, dK/dV, the row-local rest) instead of 8 and 9 on the dependent
-# chain (ops.gpt_block_*, csrc/gpt_block.hip).  MMFN_GPT_FUSED: "1" (default) both passes, "fwd" forward only, "0" off.
-GPT_FUSED = os.environ.get("MMFN_GPT_FUSED", "1")
+# chain (ops.gpt_block_*, csrc/gpt_block.hip): step 31.00 -> 29.98 ms.
 
 
 def _dw_db(dy, x, gw, gb):
@@ -719,15 +697,18 @@ class GPT(object):
         S_a, S_a2 = bufs.get(nm + ".S.a", (nb, M, C), adt), bufs.get(nm + ".S.a2", (nb, M, C), adt)
         S_o, S_h = bufs.get(nm + ".S.att", (nb, M, C), adt), bufs.get(nm + ".S.h", (nb, M, 4 * C), adt)
         self.stacks = (S_a, S_a2, S_o, S_h)
-        fold = (not ctx.bf16) and ops.current_precision() == "f32" and self.blocks[0]["fold"] is not None and M % 64 == 0 \
-            and ctx.engine.ln_fold_now(ctx.training)
-        self.folded_fwd = fold
-        fused = self.fused_now(ctx) and not fold          # fp32: both fused launches; bf16 mode: the row-block launch after attention16
-        self.fused_fwd = fused
+        # the path of this pass, which GPT.bwd follows: "fold" (eval only), "fused" (fp32: both fused launches; bf16 mode: the
+        # row-block launch after attention16) or "plain" (the per-op launches)
+        if (not ctx.bf16) and ops.current_precision() == "f32" and self.blocks[0]["fold"] is not None and M % 64 == 0 \
+                and ctx.engine.ln_fold_now(ctx.training):
+            self.path = "fold"
+        else:
+            self.path = "fused" if self.fused_now(ctx) else "plain"
+        fold = self.path == "fold"
         for i, blk in enumerate(self.blocks):
             sb = self.stream_base + 1 + 3 * i
             qkv = bufs.get("%s.b%d.qkv" % (nm, i), (M, 3 * C), adt)
-            if fused:
+            if self.path == "fused":
                 ln1, ln2 = blk["ln1"], blk["ln2"]
                 mu1, rs1 = bufs.get(ln1.name + ".mu", (M,)), bufs.get(ln1.name + ".rs", (M,))
                 mu2, rs2 = bufs.get(ln2.name + ".mu", (M,)), bufs.get(ln2.name + ".rs", (M,))
@@ -753,7 +734,7 @@ class GPT(object):
                 x = x2
                 continue
             if fold:
-                # LN(x) . Wqkv^T + b in one launch; a = LN(x) is (re)computed by the backward's side work, where it is needed
+                # LN(x) . Wqkv^T + b in one launch; a = LN(x) is never formed
                 ln = blk["ln1"]
                 mu, rs = bufs.get(ln.name + ".mu", (M,)), bufs.get(ln.name + ".rs", (M,))
                 wf, c1, c2 = blk["fold"][:3]
@@ -792,8 +773,7 @@ class GPT(object):
 
     def fused_now(self, ctx):
         """The fused block kernels serve this transformer in this pass: fp32 mode and arithmetic, n_embd 64 / 128, 4 heads, T = 192."""
-        return (GPT_FUSED != "0" and (ctx.bf16 or ops.current_precision() == "f32")
-                and ops.gpt_block_rows_supported(self.C, self.T))
+        return (ctx.bf16 or ops.current_precision() == "f32") and ops.gpt_block_rows_supported(self.C, self.T)
 
     def fused_attn_now(self, ctx):
         """... and the attention launch with the projections as its prologue too (fp32, 4 heads, 192 tokens)."""
@@ -896,8 +876,10 @@ class GPT(object):
 
     def bwd(self, ctx, g_y):
         """g_y: [B,T,C] gradient of the GPT output.  Returns the token gradient (masked by the
-        embedding dropout) to be spread back over the feature maps; writes all parameter grads."""
-        if GPT_FUSED == "1" and self.fused_now(ctx):
+        embedding dropout) to be spread back over the feature maps; writes all parameter grads.  Follows the path of the forward."""
+        if self.path == "fold":
+            raise RuntimeError("%s: no backward after a LayerNorm-folded (eval-mode) forward: it keeps no normalised tensor" % self.name)
+        if self.path == "fused":
             return self._bwd_fused(ctx, g_y)
         B = g_y.shape[0]
         T, C, nh, hs = self.T, self.C, self.nh, self.hs
@@ -935,12 +917,7 @@ class GPT(object):
         # gradient) to ONE launch at the end of this transformer (mmfn_layernorm_bwd_finalize_batched_f32) instead of one each on the
         # side streams.  Bit-identical either way; measured (3 interleaved runs each): bf16 step 17.14 -> 17.09 ms, fp32 31.40 -> 31.49
         # (there the launch at the tail costs more than the side streams gain) - hence by mode.
-        fins = [] if (ctx.bf16 and ctx.side is not None and DEFER_LN_REDUCTIONS) else None
-        refold = getattr(self, "folded_fwd", False)   # the forward ran ln1 / ln2 inside the QKV / mlp.0 GEMMs (LN_FOLD)
-        # (one scratch pair per closure site and block parity: consecutive blocks' side work alternates between TWO side streams for
-        # C <= SIDE_SPLIT_MAX_C, so a shared pair would be written concurrently)
-        scr = [[(bufs.get("%s.ln.scratch.mu%d%d" % (nm, site, par), (M,)), bufs.get("%s.ln.scratch.rs%d%d" % (nm, site, par), (M,)))
-                for par in range(2)] for site in range(2)] if refold else None
+        fins = [] if (ctx.bf16 and ctx.side is not None) else None
         g = self.ln_f.bwd(ctx, g_y.view(M, C), out=G[nblk - 1], dropped=GD[nblk - 1] if drop else None, drop_p=p_resid,
                           rng_stream=sb_of(nblk - 1) + 2, colsum=self.blocks[nblk - 1]["fc2"].gb, defer=side, collect=fins)
         for i in range(nblk - 1, -1, -1):
@@ -966,12 +943,8 @@ class GPT(object):
             if ghpart is not None:
                 side.append(lambda gh=gh, blk=blk, a2=a2, p=ghpart, r=ghrows: (ops16.colsum_partials(p, r, 4 * C, blk["fc1"].gb),
                                                                                ops.linear_dw(gh, a2, out=blk["fc1"].gw)))
-            elif refold:
-                # the forward folded ln2 into mlp.0's GEMM: the normalised tensor the weight gradient contracts with is made here
-                side.append(lambda gh=gh, blk=blk, a2=a2, x1=x1, sc=scr[0][i & 1]: (ops.layernorm_fwd(x1, blk["ln2"].w, blk["ln2"].b, a2, sc[0], sc[1]),
-                                                                  _dw_db(gh, a2, blk["fc1"].gw, blk["fc1"].gb)))
             else:
-                side.append(lambda gh=gh, blk=blk, a2=a2: (_dw_db(gh, a2, blk["fc1"].gw, blk["fc1"].gb)))
+                side.append(lambda gh=gh, blk=blk, a2=a2: _dw_db(gh, a2, blk["fc1"].gw, blk["fc1"].gb))
             ga2 = bufs.get(nm + ".ga", (M, C), adt)
             ops.linear_dx(gh, Wb(blk["fc1"]), out=ga2)
             g1 = blk["ln2"].bwd(ctx, ga2, dres=g, out=G1[i], dropped=GD2[i] if drop else None, drop_p=p_resid,
@@ -985,11 +958,7 @@ class GPT(object):
             delta = bufs.get(nm + ".delta", (B, nh, T))
             ops.attention_bwd(qkv[:, C:], qkv, qkv[:, 2 * C:], 3 * C, o, go, C, lse, delta, dqkv[:, C:], dqkv, dqkv[:, 2 * C:],
                               3 * C, B, T, nh, hs, scale, drop_p=p_attn, rng_state=ctx.rng_state, rng_stream=sb)
-            if refold:
-                side.append(lambda dqkv=dqkv, blk=blk, a=a, x=x, sc=scr[1][i & 1]: (ops.layernorm_fwd(x, blk["ln1"].w, blk["ln1"].b, a, sc[0], sc[1]),
-                                                                  _dw_db(dqkv, a, blk["g_wqkv"], blk["g_bqkv"])))
-            else:
-                side.append(lambda dqkv=dqkv, blk=blk, a=a: (_dw_db(dqkv, a, blk["g_wqkv"], blk["g_bqkv"])))
+            side.append(lambda dqkv=dqkv, blk=blk, a=a: _dw_db(dqkv, a, blk["g_wqkv"], blk["g_bqkv"]))
             ga = bufs.get(nm + ".ga2", (M, C), adt)
             ops.linear_dx(dqkv, blk["wqkv16t"] if ctx.bf16 else blk["wqkv"], out=ga)
             g = blk["ln1"].bwd(ctx, ga, dres=g1, out=G[i - 1] if i > 0 else bufs.get(nm + ".g_tok", (M, C), sdt),
@@ -1425,9 +1394,8 @@ class Engine(object):
         if self.act_dtype == torch.bfloat16:
             self.gemm_dtype = "f32"   # the fp32 islands of the bf16 mode (stems, VectorNet, head) are plain fp32
             self._build_shadows()
-        self.ln_fold_table = None
-        self.ln_fold_mode = LN_FOLD if LN_FOLD in ("eval", "1") else "0"
-        if self.ln_fold_mode != "0" and self.act_dtype == torch.float32:
+        self.ln_fold_table = None   # the LayerNorm fold of the fp32 eval forwards (GPT.fwd); None = never fold
+        if self.act_dtype == torch.float32:
             self._build_ln_fold()
         self.wino_layers = {}     # ConvBN name -> (filter storage, transformed-filter buffer): filled by the first training forward
         self.wino_table = None
@@ -1445,7 +1413,7 @@ class Engine(object):
 
     # ------------------------------------------------------------------ LayerNorm folded into the Linear behind it (fp32 path)
     def ln_fold_now(self, training):
-        return self.ln_fold_table is not None and (self.ln_fold_mode == "1" or not training)
+        return self.ln_fold_table is not None and not training
 
     def _build_ln_fold(self):
         """Per transformer block: (Wqkv . diag(gamma1), c1, c2) and (W_mlp0 . diag(gamma2), c1, c2) for MMFN_EPI_LN_FOLD, refreshed by

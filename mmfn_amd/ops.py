@@ -418,9 +418,6 @@ def linear_dx(dy, w, out=None, **epi):
     return gemm(dy, w, out, M, K, N, dy.stride(0), w.stride(0), out.stride(0), A_ROWMAJOR, B_KN, **epi)
 
 
-FUSE_COLSUM = os.environ.get("MMFN_FUSE_COLSUM", "1") != "0"   # bias gradients from the weight-gradient GEMM (MMFN_EPI_COLSUM_A)
-
-
 def linear_dw(dy, x, out=None, db=None, **epi):
     """dw[N,K] = dy[M,N]^T @ x[M,K];  db ([N], optional) = the column sums of dy = the bias gradient: formed inside the same GEMM
     where the fast TN kernel runs (fp32, 16-byte aligned operands, M a multiple of 16, N and K multiples of 4), else by colsum()."""
@@ -433,7 +430,7 @@ def linear_dw(dy, x, out=None, db=None, **epi):
     if out is None:
         out = torch.empty(N, K, dtype=torch.float32, device=dy.device)
     if db is not None:
-        fusable = (FUSE_COLSUM and _gemm_dtype == "f32" and M % 16 == 0 and N % 4 == 0 and K % 4 == 0 and N >= 4 and K >= 4
+        fusable = (_gemm_dtype == "f32" and M % 16 == 0 and N % 4 == 0 and K % 4 == 0 and N >= 4 and K >= 4
                    and dy.stride(0) % 4 == 0 and x.stride(0) % 4 == 0 and dy.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0)
         if not fusable:
             colsum(dy, db)
@@ -1293,10 +1290,7 @@ def shadow_transpose(table, n, total):
     _call("mmfn_shadow_transpose_bf16", ptr(table), n, total, stream())
 
 
-# ---------------------------------------------------------------- 7x7 stems: explicit im2col + plain GEMM
-STEM_IM2COL = True   # the 7x7 stems as explicit im2col + plain GEMM (engine.ConvBN.stem_conv)
-
-
+# ---------------------------------------------------------------- 7x7 stems: explicit im2col + plain GEMM (engine.ConvBN.stem_conv)
 def im2col_small(x, col, kh, kw, stride, pad):
     B, H, W, Cin = x.shape
     _call("mmfn_im2col_small", ptr(x), ptr(col), 1 if col.dtype == BF16 else 0, B, H, W, Cin, kh, kw, stride, pad, col.shape[1], stream())

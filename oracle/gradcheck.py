@@ -101,8 +101,9 @@ def stage_bar(cos_cpu, factor=4.0):
     decided by rounding-level details of its forward.  Measured when the narrow transformers' forward became the fused kernels (their
     tensors agree with the separate kernels' to 1e-7 and are exactly as far from fp64: tools/experiments/gpt_block_accuracy.py):
     per-group 1 - cos moved by up to 2.5e-5 in BOTH directions ((1, img) 3.8e-5 -> 3.3e-5, (3, gpt) 2.2e-5 -> 4.5e-5, (0, map) 5e-6 ->
-    1.3e-5) with the backward untouched (MMFN_GPT_FUSED=fwd vs 0).  The (0, map) group is where the oracle's own draw is unusually
-    lucky (1.5e-6, its sibling trunks 7e-6), so a purely multiplicative bar there measures the oracle's luck, not the HIP path."""
+    1.3e-5) with the backward untouched (fused vs per-op forward, both with the per-op backward).  The (0, map) group is where the
+    oracle's own draw is unusually lucky (1.5e-6, its sibling trunks 7e-6), so a purely multiplicative bar there measures the oracle's
+    luck, not the HIP path."""
     bar = 1.0 - factor * (1.0 - cos_cpu) - 1e-5
     if cos_cpu >= 0.9999:
         bar = max(bar, 0.999)

@@ -544,53 +544,29 @@ def test_batchnorm_apply_inside_the_winograd_input_transform_changes_no_bit(vari
 
 
 @pytest.mark.parametrize("variant", ["vec", "rad"])
-def test_layernorm_inside_the_qkv_and_mlp_gemms_tracks_the_separate_launches(variant, monkeypatch):
-    """MMFN_LN_FOLD (fp32 path; default: eval-mode forwards only, "1": training steps too): ln1 -> key/query/value and ln2 -> mlp.0 of every transformer block run as one GEMM
-    launch each (MMFN_EPI_LN_FOLD), the normalised tensors the weight gradients need are recomputed on the side stream in the
-    backward.  Different rounding, same function: train loss, eval waypoints and the transformer outputs agree with the
-    LayerNorm-launch path to fp32 accuracy, the weight gradients of the folded Linears to the accuracy the forward allows, and the
-    forward really has no LayerNorm launch per block (the tensors are made in the backward)."""
-    from mmfn_amd import engine as E
+def test_layernorm_folded_into_eval_forwards_tracks_the_separate_launches(variant):
+    """fp32 eval-mode forwards run ln1 -> key/query/value and ln2 -> mlp.0 of every transformer block as one GEMM launch each
+    (MMFN_EPI_LN_FOLD).  Different rounding, same function: the eval waypoints, the transformer outputs and the saved LayerNorm
+    statistics agree with the LayerNorm-launch path (the same engine with its fold tables dropped) to fp32 accuracy.  Training
+    steps never fold: with or without fold tables the loss and every gradient are the same bits."""
     from oracle import harness
     oracle, net_a, batch, args = _setup(variant)
-    monkeypatch.setattr(E, "LN_FOLD", "0")
-    net_a._engine_for()
-    monkeypatch.setattr(E, "LN_FOLD", "1")
     _, net_b, _, _ = _setup(variant)
     ea, eb = net_a._engine_for(), net_b._engine_for()
-    assert ea.ln_fold_table is None and eb.ln_fold_table is not None
+    assert ea.ln_fold_table is not None and eb.ln_fold_table is not None
+    ea.ln_fold_table = None   # the reference: every LayerNorm its own launch
     dargs = _dev_args(args)
     gt = batch["gt_wp"].to(DEV)
     net_a.train(); net_b.train()
     inp_a, inp_b = net_a._pack(*dargs), net_b._pack(*dargs)
     _, la = ea.forward(inp_a, True, gt)
     _, lb = eb.forward(inp_b, True, gt)
-    assert eb.gpts[0].folded_fwd and not getattr(ea.gpts[0], "folded_fwd", False)
-    assert abs(la.item() - lb.item()) <= 2e-6 * max(1.0, abs(la.item())), (la.item(), lb.item())
-    for k in ("gpt1", "gpt2", "gpt3", "gpt4"):
-        ta, tb = ea.taps[k], eb.taps[k]
-        # (gpt4 sits behind four fusion stages and three ResNet stages of train-mode BatchNorms: with the closed-form fill a 1e-6
-        # difference in transformer 1 arrives as ~3e-4 - measured; the loss above and the oracle comparisons below are the bar)
-        assert (ta - tb).abs().max().item() <= 1e-3 * ta.abs().max().item(), (k, (ta - tb).abs().max().item(), ta.abs().max().item())
-    # the saved statistics are the LayerNorm kernel's to rounding (first transformer: the later ones see inputs that already differ
-    # by the amplified rounding noted above)
-    for ga, gb in zip(ea.gpts[:1], eb.gpts[:1]):
-        for ba, bb in zip(ga.blocks, gb.blocks):
-            for ln in ("ln1", "ln2"):
-                assert (ba[ln].saved[1] - bb[ln].saved[1]).abs().max().item() <= 1e-5
-                assert ((ba[ln].saved[2] - bb[ln].saved[2]) / ba[ln].saved[2]).abs().max().item() <= 5e-5
+    assert all(g.path in ("fused", "plain") for g in ea.gpts + eb.gpts), [g.path for g in eb.gpts]
     ea.backward(); eb.backward()
     torch.cuda.synchronize()
+    assert torch.equal(la, lb), (la.item(), lb.item())
     La, Lb = net_a._layout, net_b._layout
-    # at batch 2 with the closed-form fill the backward amplifies the forward's rounding difference (DESIGN.md section 2): the deep
-    # stage, which the amplification has not reached, must agree closely; the folded Linears' own gradients likewise
-    b0, e0 = La.stage_ranges[0]
-    x, y = La.grads[b0:e0].double(), Lb.grads[b0:e0].double()
-    assert float((x * y).sum() / (x.norm() * y.norm())) >= 0.99999
-    for name in ("encoder.transformer4.blocks.7.attn.key.weight", "encoder.transformer4.blocks.7.mlp.0.weight",
-                 "encoder.transformer4.blocks.7.ln1.weight", "encoder.transformer4.blocks.0.ln2.bias"):
-        x, y = La.grad_views[name].double().flatten(), Lb.grad_views[name].double().flatten()
-        assert float((x * y).sum() / (x.norm() * y.norm())) >= 0.9999, name
+    assert torch.equal(La.grads[:La.tail], Lb.grads[:Lb.tail])
     # eval forward (calibrated running statistics), as the agents run it
     harness.calibrate_bn(oracle, args)
     for net in (net_a, net_b):
@@ -599,4 +575,17 @@ def test_layernorm_inside_the_qkv_and_mlp_gemms_tracks_the_separate_launches(var
     with torch.no_grad():
         ref = oracle(*args)
         oa, ob = net_a(*dargs).cpu(), net_b(*dargs).cpu()
+    assert all(g.path == "fold" for g in eb.gpts) and not any(g.path == "fold" for g in ea.gpts)
+    for k in ("gpt1", "gpt2", "gpt3", "gpt4"):
+        ta, tb = ea.taps[k], eb.taps[k]
+        # (a rounding difference in transformer 1 grows through the later fusion and ResNet stages: gpt4 is several times further
+        # apart than gpt1; the waypoint comparisons below are the bar)
+        assert (ta - tb).abs().max().item() <= 1e-3 * ta.abs().max().item(), (k, (ta - tb).abs().max().item(), ta.abs().max().item())
+    # the saved statistics are the LayerNorm kernel's to rounding (first transformer: the later ones see inputs that already differ
+    # by the amplified rounding noted above)
+    for ga, gb in zip(ea.gpts[:1], eb.gpts[:1]):
+        for ba, bb in zip(ga.blocks, gb.blocks):
+            for ln in ("ln1", "ln2"):
+                assert (ba[ln].saved[1] - bb[ln].saved[1]).abs().max().item() <= 1e-5
+                assert ((ba[ln].saved[2] - bb[ln].saved[2]) / ba[ln].saved[2]).abs().max().item() <= 5e-5
     assert (oa - ref).abs().max().item() <= 1e-4 and (ob - ref).abs().max().item() <= 1e-4
