@@ -509,6 +509,24 @@ int mmfn_adamw_groups_f32(float* p, const float* g, float* m, float* v, int64_t 
 int mmfn_adamw_groups_coef_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of,
                                const float* hyper, int n_groups, const int64_t* step, const float* coef, void* stream);
 
+/* ---- weight averaging (torch.optim.swa_utils.AveragedModel: EMA / SWA) ---------------------------------------------- */
+#define MMFN_AVG_EMA 0 /* w = *ema_w: fp32(1 - decay), formed on the host as torch forms it */
+#define MMFN_AVG_SWA 1 /* w = 1 / (*n_averaged + 1), in fp32 on the device (ema_w may be NULL) */
+/* avg = src when *n_averaged == 0 (the first update copies), else ATen's lerp(avg, src, w): avg + w * (src - avg) for |w| < 0.5,
+ * src - (src - avg) * (1 - w) otherwise.  avg, src: n floats, n % 4 == 0, 16-byte aligned; n_averaged (int64) and ema_w in device
+ * memory, so a captured hipGraph stays valid when the decay changes; *n_averaged is NOT advanced (mmfn_step_advance does that
+ * after the update).  Else MMFN_EINVAL. */
+int mmfn_weight_average_f32(float* avg, const float* src, int64_t n, const int64_t* n_averaged, const float* ema_w, int mode,
+                            void* stream);
+/* mmfn_adamw_groups_f32 / mmfn_adamw_groups_coef_f32 that also fold each NEW parameter into avg[0, n) as mmfn_weight_average_f32
+ * does (one pass: +8 B per parameter) */
+int mmfn_adamw_groups_avg_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of, const float* hyper,
+                              int n_groups, const int64_t* step, float* avg, const int64_t* n_averaged, const float* ema_w, int mode,
+                              void* stream);
+int mmfn_adamw_groups_coef_avg_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of,
+                                   const float* hyper, int n_groups, const int64_t* step, const float* coef, float* avg,
+                                   const int64_t* n_averaged, const float* ema_w, int mode, void* stream);
+
 /* ---- gradient accumulation and global-norm clipping over the flat gradient buffer ------------------------------ */
 #define MMFN_ACCUM_NONE 0 /* read g only (needs partials) */
 #define MMFN_ACCUM_ADD 1  /* acc += g */

@@ -77,13 +77,42 @@ extern "C" int mmfn_adamw_f32(float* p, const float* g, float* m, float* v, int6
 namespace {
 struct GroupScalars { float step_size, decay, bc2_sqrt, beta1, beta2, eps, grad_scale, pad; };
 
+// ---- weight averaging (torch.optim.swa_utils.AveragedModel) --------------------------------------------------------------
+// avg = src at the first update (*n_averaged == 0), else ATen's lerp(avg, src, w).  w as torch forms it: EMA lerps with the
+// Python float 1 - decay rounded to fp32 (the host writes it to *ema_w), SWA with 1 / (n_averaged + 1), the reciprocal of an
+// int64 tensor in fp32.  Both live in device memory: a captured step stays valid when the decay changes or the count grows.
+struct AvgArgs {
+  float* avg;
+  const int64_t* n_averaged;
+  const float* ema_w;
+  int mode;
+};
+
+__device__ inline float avg_weight(const AvgArgs& a) {
+  return a.mode == MMFN_AVG_EMA ? *a.ema_w : 1.0f / (float)(*a.n_averaged + 1);
+}
+
+// at::lerp (ATen/native/Lerp.h): the small-weight form below 0.5, the large-weight form from the end point above
+__device__ inline float lerp_aten(float a, float p, float w) {
+  return fabsf(w) < 0.5f ? a + w * (p - a) : p - (p - a) * (1.0f - w);
+}
+
+__device__ inline f32x4 lerp4(f32x4 a, f32x4 p, float w) {
+  f32x4 r;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) r[e] = lerp_aten(a[e], p[e], w);
+  return r;
+}
+
 // COEF: every group's grad_scale is multiplied by *coef (the clip_grad_norm_ coefficient, written on the device by
-// mmfn_grad_norm_finalize); COEF = false is the plain grouped step
-template <bool COEF>
+// mmfn_grad_norm_finalize); COEF = false is the plain grouped step.  AVG: the new parameter is also folded into avg.avg
+// (the weight average), from registers: 8 B more per parameter instead of a 12 B pass of its own
+template <bool COEF, bool AVG>
 __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                            float* __restrict__ v, int64_t n, const uint8_t* __restrict__ group_of,
                                                            const float* __restrict__ hyper, int n_groups,
-                                                           const int64_t* __restrict__ step, const float* __restrict__ coef) {
+                                                           const int64_t* __restrict__ step, const float* __restrict__ coef,
+                                                           AvgArgs avg) {
   __shared__ GroupScalars gs[MMFN_ADAMW_MAX_GROUPS];
   if ((int)threadIdx.x < n_groups) {
     const float* h = hyper + threadIdx.x * 8;
@@ -116,7 +145,40 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p
     *reinterpret_cast<f32x4*>(p + i * 4) = pv;
     *reinterpret_cast<f32x4*>(m + i * 4) = mv;
     *reinterpret_cast<f32x4*>(v + i * 4) = vv;
+    if (AVG) {   // the count and the weight are uniform loads: the first update copies the new parameter, later ones lerp
+      // an empty asm makes the new parameter opaque here: without it the compiler packs and contracts the AdamW arithmetic
+      // above differently once the lerp also reads it, and the step stops being bit-identical to the plain instance
+      f32x4 out = pv;
+      asm volatile("" : "+v"(out));
+      pv = out;
+      if (*avg.n_averaged != 0) out = lerp4(*reinterpret_cast<const f32x4*>(avg.avg + i * 4), pv, avg_weight(avg));
+      *reinterpret_cast<f32x4*>(avg.avg + i * 4) = out;
+    }
   }
+}
+
+__global__ __launch_bounds__(256) void weight_average_kernel(const float* __restrict__ src, int64_t n4, AvgArgs avg) {
+  const bool copy = *avg.n_averaged == 0;
+  const float w = copy ? 1.0f : avg_weight(avg);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    f32x4 out = *reinterpret_cast<const f32x4*>(src + i * 4);
+    if (!copy) out = lerp4(*reinterpret_cast<const f32x4*>(avg.avg + i * 4), out, w);
+    *reinterpret_cast<f32x4*>(avg.avg + i * 4) = out;
+  }
+}
+
+int adamw_blocks(int64_t n) { return (int)std::min<int64_t>(ceil_div64(n / 4, 256), 4096); }
+
+bool adamw_args_ok(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, int n_groups, const int64_t* step) {
+  return step && hyper && n_groups >= 1 && n_groups <= MMFN_ADAMW_MAX_GROUPS && !(n & 3) &&
+         !(((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15);
+}
+
+// the average: 16-byte aligned floats, the count (and for EMA the weight) in device memory, a known mode
+bool avg_args_ok(const AvgArgs& a) {
+  if (a.mode != MMFN_AVG_EMA && a.mode != MMFN_AVG_SWA) return false;
+  if (!a.avg || ((uintptr_t)a.avg & 15) || !a.n_averaged || ((uintptr_t)a.n_averaged & 7)) return false;
+  return a.mode != MMFN_AVG_EMA || (a.ema_w && !((uintptr_t)a.ema_w & 3));
 }
 }  // namespace
 
@@ -127,8 +189,8 @@ extern "C" int mmfn_adamw_groups_f32(float* p, const float* g, float* m, float* 
       (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15))
     return MMFN_EINVAL;
   const int blocks = (int)std::min<int64_t>(ceil_div64(n / 4, 256), 4096);
-  hipLaunchKernelGGL(adamw_groups_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, group_of, hyper,
-                     n_groups, step, (const float*)nullptr);
+  hipLaunchKernelGGL((adamw_groups_kernel<false, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, group_of,
+                     hyper, n_groups, step, (const float*)nullptr, AvgArgs{});
   MMFN_LAUNCH_CHECK();
   return 0;
 }
@@ -140,8 +202,42 @@ extern "C" int mmfn_adamw_groups_coef_f32(float* p, const float* g, float* m, fl
       (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15))
     return MMFN_EINVAL;
   const int blocks = (int)std::min<int64_t>(ceil_div64(n / 4, 256), 4096);
-  hipLaunchKernelGGL(adamw_groups_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, group_of, hyper,
-                     n_groups, step, coef);
+  hipLaunchKernelGGL((adamw_groups_kernel<true, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, group_of,
+                     hyper, n_groups, step, coef, AvgArgs{});
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mmfn_adamw_groups_avg_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of,
+                                         const float* hyper, int n_groups, const int64_t* step, float* avg, const int64_t* n_averaged,
+                                         const float* ema_w, int mode, void* stream) {
+  if (n <= 0) return 0;
+  const AvgArgs a{avg, n_averaged, ema_w, mode};
+  if (!adamw_args_ok(p, g, m, v, n, hyper, n_groups, step) || !avg_args_ok(a)) return MMFN_EINVAL;
+  hipLaunchKernelGGL((adamw_groups_kernel<false, true>), dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
+                     group_of, hyper, n_groups, step, (const float*)nullptr, a);
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mmfn_adamw_groups_coef_avg_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of,
+                                              const float* hyper, int n_groups, const int64_t* step, const float* coef, float* avg,
+                                              const int64_t* n_averaged, const float* ema_w, int mode, void* stream) {
+  if (n <= 0) return 0;
+  const AvgArgs a{avg, n_averaged, ema_w, mode};
+  if (!coef || !adamw_args_ok(p, g, m, v, n, hyper, n_groups, step) || !avg_args_ok(a)) return MMFN_EINVAL;
+  hipLaunchKernelGGL((adamw_groups_kernel<true, true>), dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
+                     group_of, hyper, n_groups, step, coef, a);
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mmfn_weight_average_f32(float* avg, const float* src, int64_t n, const int64_t* n_averaged, const float* ema_w, int mode,
+                                       void* stream) {
+  if (n <= 0) return 0;
+  const AvgArgs a{avg, n_averaged, ema_w, mode};
+  if (!src || ((uintptr_t)src & 15) || (n & 3) || !avg_args_ok(a)) return MMFN_EINVAL;
+  hipLaunchKernelGGL(weight_average_kernel, dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, src, n / 4, a);
   MMFN_LAUNCH_CHECK();
   return 0;
 }

@@ -1408,6 +1408,7 @@ class Engine(object):
         self.accum_pending = 0      # micro-steps in grad_acc (host count: it picks the 1 / (k * world) of the final step)
         self._norm = None           # partials table, its slots, and the device (norm, coef) pair
         self._tiling_checked = False
+        self.average = None         # averaging.AveragedMMFN updated inside every optimizer step's AdamW launch (attach_average)
         self.n_lanes = int(os.environ.get("MMFN_BRANCH_LANES", "3"))
         self.offload_wgrad = True   # transformer weight / bias gradients on the side stream (worth 3.9 ms per step)
 
@@ -1790,8 +1791,36 @@ class Engine(object):
         self.set_hyper(groups)
         self.module.weights_changed()
         ops.step_advance(self.step_count)
+        group_of = self.opt_group_of if len(groups) > 1 else None
+        if self.average is not None:
+            self._adamw_average(len(groups), group_of)
+            return
         ops.adamw_groups(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self.step_count, self.opt_hyper, len(groups),
-                         group_of=self.opt_group_of if len(groups) > 1 else None, n=L.tail)
+                         group_of=group_of, n=L.tail)
+
+    # ------------------------------------------------------------------ weight average (mmfn_amd.averaging)
+    def attach_average(self, avg):
+        """From now on every optimizer step of the fused path (optimizer_step, final_adam: eager, graph-replayed, data parallel)
+        also updates `avg` inside its AdamW launch; accumulate_step micro-steps do not.  A captured step records whether an
+        average was attached and refuses to replay after that changed (parallel.GraphedStep)."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("attach_average() inside a hipGraph capture")
+        avg.check_model(self.module)
+        avg.copy_tail(self.module)
+        self.average = avg
+
+    def detach_average(self):
+        self.average = None
+
+    def _adamw_average(self, n_groups, group_of, coef=None):
+        """The AdamW launch with the attached average folded in (coef: the clipping instance), then the average's BatchNorm
+        buffers and its count: three launches (+ a counter copy) instead of one."""
+        L, a = self.layout, self.average
+        ops.adamw_groups_avg(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self.step_count, self.opt_hyper, n_groups,
+                             a.module._layout.params, a.n_averaged, a.ema_weight, a.mode_code, group_of=group_of, coef=coef, n=L.tail)
+        a.update_buffers(self.module)
+        ops.step_advance(a.n_averaged)
+        a.module.weights_changed()
 
     def backward_and_step(self, dp=None, lr=1e-4, **adam):
         """Backward of the last training forward + AdamW (+ the gradient all-reduces of `dp`, issued from the streams that
@@ -1963,8 +1992,13 @@ class Engine(object):
                 part = nm["partials"][:nm["n_group_slots"]]
             out = nm["out"]
             ops.grad_norm_finalize(part, self.opt_hyper[0, 5:6], self.opt_hyper[0, 6:7], out[0:1], out[1:2])
-            ops.adamw_groups_coef(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self.step_count, self.opt_hyper, n_groups, out[1:2],
-                                  group_of=group_of, n=L.tail)
+            if self.average is not None:
+                self._adamw_average(n_groups, group_of, coef=out[1:2])
+            else:
+                ops.adamw_groups_coef(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self.step_count, self.opt_hyper, n_groups, out[1:2],
+                                      group_of=group_of, n=L.tail)
+        elif self.average is not None:
+            self._adamw_average(n_groups, group_of)
         else:
             ops.adamw_groups(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self.step_count, self.opt_hyper, n_groups,
                              group_of=group_of, n=L.tail)

@@ -187,6 +187,15 @@ class MMFN(nn.Module):
         (engine.Engine.accumulate_step)."""
         return self._engine_for().accumulate_step(inp, gt_wp)
 
+    def attach_average(self, average):
+        """Update `average` (mmfn_amd.averaging.AveragedMMFN) inside every optimizer step of the fused path
+        (engine.Engine.attach_average); None detaches."""
+        eng = self._engine_for()
+        if average is None:
+            eng.detach_average()
+        else:
+            eng.attach_average(average)
+
     # ------------------------------------------------------------------ PID (model_vec.py:684-726)
     def control_pid(self, waypoints, velocity):
         assert waypoints.size(0) == 1

@@ -1135,6 +1135,30 @@ def adamw_groups_coef(p, g, m, v, step, hyper, n_groups, coef, group_of=None, n=
           stream())
 
 
+AVG_EMA, AVG_SWA = 0, 1   # mirror include/mmfn_hip.h
+
+
+def weight_average(avg, src, n_averaged, ema_weight, mode):
+    """avg = src (first update: *n_averaged == 0) or ATen's lerp(avg, src, w) over avg.numel() floats; w = *ema_weight (EMA) or
+    1 / (*n_averaged + 1) (SWA), both read on the device.  Does not advance n_averaged."""
+    if src.numel() < avg.numel():
+        raise ValueError("source holds %d floats, the average %d" % (src.numel(), avg.numel()))
+    _call("mmfn_weight_average_f32", ptr(avg), ptr(src), avg.numel(), ptr(n_averaged), ptr(ema_weight), int(mode), stream())
+
+
+def adamw_groups_avg(p, g, m, v, step, hyper, n_groups, avg, n_averaged, ema_weight, mode, group_of=None, coef=None, n=None):
+    """adamw_groups (coef: adamw_groups_coef) that also folds every new parameter into avg[0, n) as weight_average does."""
+    n = p.numel() if n is None else n
+    if avg.numel() < n:
+        raise ValueError("average holds %d floats, the step covers %d" % (avg.numel(), n))
+    if coef is None:
+        _call("mmfn_adamw_groups_avg_f32", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(group_of), ptr(hyper), n_groups, ptr(step), ptr(avg),
+              ptr(n_averaged), ptr(ema_weight), int(mode), stream())
+    else:
+        _call("mmfn_adamw_groups_coef_avg_f32", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(group_of), ptr(hyper), n_groups, ptr(step),
+              ptr(coef), ptr(avg), ptr(n_averaged), ptr(ema_weight), int(mode), stream())
+
+
 ACCUM_NONE, ACCUM_ADD, ACCUM_FOLD = 0, 1, 2   # mirror include/mmfn_hip.h
 
 

@@ -90,6 +90,16 @@ class DataParallel(object):
             self.dist.broadcast(eng.step_count, src)
             self.dist.broadcast(eng.rng_state, src)
             eng.rng_state[0] += self.dist.get_rank()  # per-rank dropout streams
+            if eng.average is not None:
+                self.broadcast_average(eng.average, src)
+
+    def broadcast_average(self, avg, src=0):
+        """A weight average (averaging.AveragedMMFN) resumed on rank `src` into every rank: flat parameters, BatchNorm buffers,
+        n_averaged and the EMA weight.  After that each rank updates its own copy from identical parameters, with no collective."""
+        A = avg.module._layout
+        for t in (A.params, A.buffers_flat, A.counters_flat, avg.n_averaged.view(1), avg.ema_weight):
+            self.dist.broadcast(t, src)
+        avg.module.weights_changed()
 
     def _staging(self):
         if self.g16 is None:
@@ -352,6 +362,7 @@ class GraphedStep(object):
             eng.optimizer_step(lr=lr, grad_scale=scale, **adam)
 
         pending = eng.accum_pending
+        self.average = eng.average   # folded into the captured AdamW launch (or not): a replay must find the same attachment
         try:
             rec.capture(body)
         finally:
@@ -367,6 +378,10 @@ class GraphedStep(object):
         pending = eng.accum_pending
         if pending and (self.variant == "step" or (self.variant == "final" and not self.fold)):
             raise RuntimeError("%d accumulated micro-step(s) are pending: this captured step would drop them" % pending)
+        if self.variant != "micro" and eng.average is not self.average:
+            raise RuntimeError("this step was captured %s; the engine now has %s: capture the step again" % (
+                "with an attached weight average" if self.average is not None else "without a weight average",
+                "a different one" if eng.average is not None else "none"))
         if self.variant == "final":
             eng.set_hyper(eng.final_rows(self.lr, pending, self.dp, self.clip, **self.adam))
         if self.dp is not None and not self.single_graph:
@@ -377,6 +392,8 @@ class GraphedStep(object):
             return self.loss
         eng.accum_pending = 0
         eng.module.weights_changed()   # the replayed AdamW does not pass through Engine.optimizer_step
+        if self.average is not None:
+            self.average.module.weights_changed()
         return self.loss
 
 

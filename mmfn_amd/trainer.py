@@ -7,6 +7,7 @@ same files in the log directory:
     best_model.pth    model.state_dict() when the validation loss improved                    (:207-211)
     best_optim.pth    optimizer.state_dict() (torch.optim.AdamW layout)                       (:209)
     model.pth, recent_optim.pth   always                                                      (:215-216)
+(a run with a weight average, averaging.AveragedMMFN, also writes averaged_model.pth and best_averaged_model.pth)
 so a run can be resumed by either implementation.  Differences, all on the host side:
   * the step is the fused one (forward + L1 + backward + bucketed all-reduce + AdamW on device buffers);
     `fused=False` runs the reference's literal sequence through autograd instead;
@@ -52,10 +53,14 @@ class Trainer(object):
         self.device = device
         self.logdir = log_dir
         self.max_captured_shapes = 12  # ragged batches (lane buckets, LiDAR sizes) multiply the shapes: bound the captures
+        # weight average (averaging.AveragedMMFN): its validation losses and best value; recent.log carries them only for runs
+        # that have an average
+        self.val_loss_average = []
+        self.bestval_average = 1e10
 
     # ------------------------------------------------------------------ one epoch of training
     def train(self, model, dataloader_train, config, optimizer, dp=None, fused=True, log_every=50, on_log=None, graph=True,
-              lane_bucket=16, accum_steps=1, clip_grad_norm=None):
+              lane_bucket=16, accum_steps=1, clip_grad_norm=None, average=None):
         """One epoch.  graph=True (fused path): the second batch of a given shape captures the step into hipGraphs over
         static input buffers and every later batch of that shape only copies its inputs and replays (the first one runs
         eagerly and sizes the buffers); lane sets are zero-padded to a multiple of `lane_bucket` lanes so that ragged
@@ -69,7 +74,25 @@ class Trainer(object):
         DistributedSampler gives every rank the same number of batches), and the gradient all-reduce runs once per group.
         clip_grad_norm = max_norm: torch.nn.utils.clip_grad_norm_ over all trained parameters before each optimizer step
         (inf: only measure); on_log then also gets "grad_norm", the last optimizer step's global norm.  Each variant of the
-        step (micro-step, group-closing step) is a captured shape of its own, bounded by max_captured_shapes."""
+        step (micro-step, group-closing step) is a captured shape of its own, bounded by max_captured_shapes.
+
+        average (averaging.AveragedMMFN): updated after every optimizer step of the epoch - attached to the engine for the
+        epoch, inside the fused step's AdamW launch (eager and replayed, captured as shapes of their own; micro-steps do not
+        update it); fused=False: its update_parameters() after each optimizer.step()."""
+        if average is None or not fused:
+            return self._train(model, dataloader_train, config, optimizer, dp, fused, log_every, on_log, graph, lane_bucket,
+                               accum_steps, clip_grad_norm, average)
+        eng = model._engine_for()
+        eng.attach_average(average)
+        try:
+            return self._train(model, dataloader_train, config, optimizer, dp, fused, log_every, on_log, graph, lane_bucket,
+                               accum_steps, clip_grad_norm, average)
+        finally:
+            eng.detach_average()
+
+    def _train(self, model, dataloader_train, config, optimizer, dp, fused, log_every, on_log, graph, lane_bucket, accum_steps,
+               clip_grad_norm, average):
+        """Trainer.train's epoch loop (an attached average is the caller's)."""
         accum_steps = int(accum_steps)
         if accum_steps < 1:
             raise ValueError("accum_steps must be >= 1, got %d" % accum_steps)
@@ -96,7 +119,7 @@ class Trainer(object):
                 inp = _bucket_lanes(inp, lane_bucket)
                 in_group += 1
                 final = in_group == accum_steps or last
-                loss = self._accum_call(eng, dp, inp, gt, lr, adam, final, accum_steps > 1, clip_grad_norm, graph)
+                loss = self._accum_call(eng, dp, inp, gt, lr, adam, final, accum_steps > 1, clip_grad_norm, graph, average)
                 if final:
                     in_group = 0
             elif fused:
@@ -108,6 +131,8 @@ class Trainer(object):
                 inp = _bucket_lanes(inp, lane_bucket)  # in both modes, so that eager and replayed steps are bit-identical
                 if graph:
                     sig = StaticBatchStep.signature(inp, gt)
+                    if average is not None:   # a capture with the average in its AdamW launch is a shape of its own
+                        sig = (sig, "average")
                     state = self._static_steps.pop(sig, None)
                     if state is None:  # first batch of this shape: eager (allocates the engine's buffers for it)
                         state = "seen"
@@ -136,6 +161,8 @@ class Trainer(object):
                 loss = torch.nn.functional.l1_loss(pred, gt, reduction="none").mean()
                 loss.backward()
                 optimizer.step()
+                if average is not None:
+                    average.update_parameters(model)
                 loss = loss.detach().view(1)
             total += loss
             window += loss
@@ -151,13 +178,15 @@ class Trainer(object):
         self.cur_epoch += 1
         return self.train_loss[-1]
 
-    def _accum_call(self, eng, dp, inp, gt, lr, adam, final, fold, clip, graph):
+    def _accum_call(self, eng, dp, inp, gt, lr, adam, final, fold, clip, graph, average=None):
         """One batch of an accumulation group: a micro-step, or (final) the step that closes the group.  graph=True: per
         (shape, variant) the first call runs eagerly, the second captures (parallel.StaticBatchStep), later ones replay."""
         if not graph:
             return eng.train_step(inp, gt, lr=lr, dp=dp, clip_grad_norm=clip, **adam) if final else eng.accumulate_step(inp, gt)
         variant = "final" if final else "micro"
         sig = (StaticBatchStep.signature(inp, gt), variant, fold, clip is not None)
+        if average is not None and final:
+            sig = sig + ("average",)
         state = self._static_steps.pop(sig, None)
         if state is not None and state != "eager":
             if state == "seen":
@@ -186,10 +215,26 @@ class Trainer(object):
         second batch of a shape captures the forward into a hipGraph over static inputs (parallel.StaticEvalStep) and later
         batches of that shape replay it; lane sets are padded to a multiple of `lane_bucket` (padded lanes are masked by
         lane_num: the loss is unchanged)."""
+        loss = self._mean_loss(model, dataloader_val, config, graph, lane_bucket, "_static_evals")
+        if loss is not None:
+            self.val_loss.append(loss)
+        return loss
+
+    def validate_average(self, average, dataloader_val, config, graph=True, lane_bucket=16):
+        """validate() of a weight average's module (averaging.AveragedMMFN) into val_loss_average; val_loss, bestval and the
+        best_* files stay the live model's."""
+        loss = self._mean_loss(average.module, dataloader_val, config, graph, lane_bucket, "_static_evals_average")
+        if loss is not None:
+            self.val_loss_average.append(loss)
+        return loss
+
+    def _mean_loss(self, model, dataloader_val, config, graph, lane_bucket, cache):
+        """Mean eval-mode L1 loss over the loader (None without batches); `cache`: the attribute holding this model's captures."""
         model.eval()
         eng = model._engine_for()
-        if not hasattr(self, "_static_evals"):
-            self._static_evals = {}      # input-shape signature -> "seen" | "eager" | StaticEvalStep, in LRU order
+        if not hasattr(self, cache):
+            setattr(self, cache, {})     # input-shape signature -> "seen" | "eager" | StaticEvalStep, in LRU order
+        static_evals = getattr(self, cache)
         total = torch.zeros(1, dtype=torch.float32, device=model._layout.device)
         num_batches = 0
         with torch.no_grad():
@@ -198,7 +243,7 @@ class Trainer(object):
                 if graph:
                     inp = _bucket_lanes(inp, lane_bucket)
                     sig = StaticBatchStep.signature(inp, gt)
-                    state = self._static_evals.pop(sig, None)
+                    state = static_evals.pop(sig, None)
                     if state is None:
                         state = "seen"
                         _, loss = eng.forward(inp, False, gt)
@@ -212,16 +257,15 @@ class Trainer(object):
                                 torch.cuda.synchronize()
                                 state = "eager"
                         loss = eng.forward(inp, False, gt)[1] if state == "eager" else state(inp, gt)
-                    self._static_evals[sig] = state
-                    while len(self._static_evals) > self.max_captured_shapes:
-                        _evict_lru(self._static_evals)
+                    static_evals[sig] = state
+                    while len(static_evals) > self.max_captured_shapes:
+                        _evict_lru(static_evals)
                 else:
                     _, loss = eng.forward(inp, False, gt)
                 total += loss
                 num_batches += 1
         if num_batches:
-            self.val_loss.append(float(total.item()) / num_batches)
-            return self.val_loss[-1]
+            return float(total.item()) / num_batches
         return None
 
     # ------------------------------------------------------------------ checkpoints
@@ -229,13 +273,24 @@ class Trainer(object):
         return {"epoch": self.cur_epoch, "iter": self.cur_iter, "bestval": self.bestval, "bestval_epoch": self.bestval_epoch,
                 "train_loss": self.train_loss, "val_loss": self.val_loss}
 
-    def save(self, model, optimizer, logdir=None):
+    def save(self, model, optimizer, logdir=None, average=None):
+        """average (averaging.AveragedMMFN): also averaged_model.pth (a plain state_dict of the reference's layout, every save),
+        best_averaged_model.pth (when the average's own validation loss improved) and, in recent.log, "average" (mode, decay,
+        use_buffers, n_averaged), "val_loss_average" and "bestval_average"."""
         logdir = logdir or self.logdir
         os.makedirs(logdir, exist_ok=True)
         best = bool(self.val_loss) and self.val_loss[-1] <= self.bestval
         if best:
             self.bestval = self.val_loss[-1]
             self.bestval_epoch = self.cur_epoch
+        if average is not None:
+            best_avg = bool(self.val_loss_average) and self.val_loss_average[-1] <= self.bestval_average
+            if best_avg:
+                self.bestval_average = self.val_loss_average[-1]
+            avg_weights = _plain_state_dict(average.module)
+            if best_avg:
+                _atomic_save(avg_weights, os.path.join(logdir, "best_averaged_model.pth"))
+            _atomic_save(avg_weights, os.path.join(logdir, "averaged_model.pth"))
         weights = _plain_state_dict(model)
         opt_state = optimizer.state_dict()
         # every file goes to a temporary name first and is renamed into place, so no file is ever torn; recent.log is written
@@ -249,8 +304,13 @@ class Trainer(object):
         _atomic_save(opt_state, os.path.join(logdir, "recent_optim.pth"))
         tmp = os.path.join(logdir, "recent.log.tmp")
         table = self._log_table()
-        table["files"] = {n: _stamp(os.path.join(logdir, n)) for n in ("model.pth", "recent_optim.pth", "best_model.pth", "best_optim.pth")
-                          if os.path.isfile(os.path.join(logdir, n))}
+        files = ("model.pth", "recent_optim.pth", "best_model.pth", "best_optim.pth")
+        if average is not None:
+            files += ("averaged_model.pth", "best_averaged_model.pth")
+            table["average"] = {"mode": average.mode, "decay": average.decay, "use_buffers": average.use_buffers,
+                                "n_averaged": int(average.n_averaged.item())}
+            table["val_loss_average"], table["bestval_average"] = self.val_loss_average, self.bestval_average
+        table["files"] = {n: _stamp(os.path.join(logdir, n)) for n in files if os.path.isfile(os.path.join(logdir, n))}
         with open(tmp, "w") as f:
             f.write(json.dumps(table))
             f.flush()
@@ -258,8 +318,10 @@ class Trainer(object):
         os.replace(tmp, os.path.join(logdir, "recent.log"))
         return best
 
-    def resume(self, model, optimizer, logdir=None, which="best"):
-        """Pick a run up from its log directory (phase2_train_net.py:288-302 loads the `best_*` pair)."""
+    def resume(self, model, optimizer, logdir=None, which="best", average=None):
+        """Pick a run up from its log directory (phase2_train_net.py:288-302 loads the `best_*` pair).  average
+        (averaging.AveragedMMFN): restored from averaged_model.pth and the counter in recent.log - the average of the last save
+        whichever pair the model comes from (best_averaged_model.pth is chosen by another loss and is for deployment)."""
         logdir = logdir or self.logdir
         path = os.path.join(logdir, "recent.log")
         if not os.path.isfile(path):
@@ -285,6 +347,13 @@ class Trainer(object):
         weights = torch.load(os.path.join(logdir, names[0]), map_location="cpu")
         model.load_state_dict({k[7:] if k.startswith("module.") else k: v for k, v in weights.items()})
         optimizer.load_state_dict(torch.load(os.path.join(logdir, names[1]), map_location="cpu"))
+        if average is not None and "average" in table and os.path.isfile(os.path.join(logdir, "averaged_model.pth")):
+            meta = table["average"]
+            average.load_state_dict({"module": torch.load(os.path.join(logdir, "averaged_model.pth"), map_location="cpu"),
+                                     "n_averaged": meta["n_averaged"], "mode": meta["mode"], "decay": meta["decay"],
+                                     "use_buffers": meta["use_buffers"]})
+            self.val_loss_average = list(table.get("val_loss_average", []))
+            self.bestval_average = table.get("bestval_average", 1e10)
         return True
 
 
@@ -372,32 +441,45 @@ def _plain_state_dict(model):
 
 
 def fit(model, optimizer, train_loader, val_loader, config, logdir, epochs, val_every=1, save_every=1, dp=None, rank=0,
-        on_log=None, dist=None, accum_steps=1, clip_grad_norm=None):
+        on_log=None, dist=None, accum_steps=1, clip_grad_norm=None, average=None, average_every="step", average_start_epoch=0):
     """The epoch loop of phase2_train_net.py:307-322: train every epoch; rank 0 validates every `val_every`
     epochs and saves every `save_every`.  Data parallel: pass `dp` (a parallel.DataParallel), or just the initialised
     torch.distributed module as `dist` - the transport is then chosen by parallel.connect: the C-ABI RCCL communicator when it
     passes its self-test on every rank (the whole step, gradient all-reduces included, replays as ONE hipGraph per batch shape),
     else torch.distributed (four graphs per step, buckets in between); a capture that fails continues eagerly.
     accum_steps / clip_grad_norm: gradient accumulation and global-norm clipping (Trainer.train; the same accum_steps on
-    every rank)."""
+    every rank).
+    average (averaging.AveragedMMFN): average_every="step" updates it in every optimizer step (inside the AdamW launch) from epoch
+    average_start_epoch on; "epoch" calls its update_parameters() at the end of each such epoch (the SWA schedule).  Rank 0 also
+    validates average.module into trainer.val_loss_average and saves averaged_model.pth / best_averaged_model.pth; every rank
+    keeps its own copy, in lock step because the parameters are (DataParallel.broadcast_average after a resume)."""
+    if average_every not in ("step", "epoch"):
+        raise ValueError("average_every must be 'step' or 'epoch', got %r" % (average_every,))
     if dp is None and dist is not None and dist.get_world_size() > 1:
         from .parallel import connect
         dp, _ = connect(model, dist)
         rank = dist.get_rank()
     trainer = Trainer(model._layout.device, logdir)
     if rank == 0:
-        trainer.resume(model, optimizer)
+        trainer.resume(model, optimizer, average=average)
     if dp is not None:
         dp.broadcast_parameters()                       # weights, BN buffers, Adam moments, step counter, RNG
         sync_resume_state(trainer, optimizer, dp.dist)  # epoch / iteration counters, loss history, lr & co
+        if average is not None:
+            dp.broadcast_average(average)
     for epoch in range(trainer.cur_epoch, epochs):
         sampler = getattr(train_loader, "sampler", None)
         if hasattr(sampler, "set_epoch"):
             sampler.set_epoch(epoch)
+        averaging = average is not None and epoch >= average_start_epoch
         trainer.train(model, train_loader, config, optimizer, dp=dp, on_log=on_log if rank == 0 else None, accum_steps=accum_steps,
-                      clip_grad_norm=clip_grad_norm)
+                      clip_grad_norm=clip_grad_norm, average=average if averaging and average_every == "step" else None)
+        if averaging and average_every == "epoch":
+            average.update_parameters(model)
         if epoch % val_every == 0 and rank == 0 and val_loader is not None:
             trainer.validate(model, val_loader, config)
+            if average is not None:
+                trainer.validate_average(average, val_loader, config)
             if epoch % save_every == 0:
-                trainer.save(model, optimizer)
+                trainer.save(model, optimizer, average=average)
     return trainer
