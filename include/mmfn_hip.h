@@ -372,6 +372,20 @@ int mmfn_colsum_batched_f32(const float* in, int batch, int64_t stride_in, int64
 /* MaxPool2d(3,2,1) with first-max argmax (uint8 tap index) — torchvision stem (model_vec.py:512,518) */
 int mmfn_maxpool3x3s2_fwd_f32(const float* x, float* y, uint8_t* idx, int B, int H, int W, int C, void* stream);
 int mmfn_maxpool3x3s2_bwd_f32(const float* gy, const uint8_t* idx, float* gx, int B, int H, int W, int C, void* stream);
+/* The ResNet stems (conv1 -> bn1 -> relu -> maxpool, model_vec.py:509-512 / :515-518; aten::native_batch_norm, aten::relu_,
+ * aten::max_pool2d_with_indices and their backwards) without the stem-resolution activation and its gradient in HBM.
+ * mmfn_stem_pool_ok: 1 when both entries below take an x [B,H,W,C] (H, W even, C as mmfn_bn_bwd_f32 takes it), else 0.
+ * fwd: y [B,H/2,W/2,C], idx = MaxPool2d(3,2,1)(relu(bn(x))) in one pass over x = the convolution output; bit-identical to
+ *      mmfn_bn_apply_f32(relu) + mmfn_maxpool3x3s2_fwd_f32 (first maximum wins, NaN as there).
+ * bwd: g [B,H/2,W/2,C] = dL/d(pooled); the BatchNorm backward's two reductions and its apply pass gather dL/d(relu output) from g
+ *      and idx (mmfn_maxpool3x3s2_bwd_f32's sum order) and recompute the ReLU sign from x (mmfn_bn_bwd_f32 with y == NULL);
+ *      dx, dweight, dbias bit-identical to mmfn_maxpool3x3s2_bwd_f32 + mmfn_bn_bwd_f32.  workspace: mmfn_norm_workspace_bytes. */
+int mmfn_stem_pool_ok(int B, int H, int W, int C);
+int mmfn_stem_bn_relu_maxpool_fwd_f32(const float* x, const float* mean, const float* rstd, const float* weight,
+                                      const float* bias, float* y, uint8_t* idx, int B, int H, int W, int C, void* stream);
+int mmfn_stem_bn_bwd_pooled_f32(const float* g, const uint8_t* idx, const float* x, int B, int H, int W, int C,
+                                const float* mean, const float* rstd, const float* weight, const float* bias, float* dx,
+                                float* dweight, float* dbias, void* workspace, void* stream);
 /* tok[b, g*64+a, :] = dropout(pos_emb + AdaptiveAvgPool2d(8,8)(frame g of sample b)[a,:] + vel_emb(velocity[b]))
  * for n_modal feature maps F_m[B*frames[m],S,S,C]: model_vec.py:527-529 + GPT.forward :223-235 in one pass.  A token
  * group g is one frame: the frames[0] frames of modality 0 (n_views*seq_len camera frames per sample), then the

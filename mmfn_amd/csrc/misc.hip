@@ -237,10 +237,13 @@ extern "C" int mmfn_shadow_transpose_bf16(const void* table, int n_entries, int6
 
 // ---------------------------------------------------------------- the 7x7 stems as explicit im2col + plain GEMM
 // conv1 of the torchvision ResNets (model_vec.py:509,515: 7x7, stride 2, 3 camera / 2 BEV channels).  With K = 49 * Cin =
-// 147 / 98 the implicit-GEMM gather spends its time on per-element tap arithmetic (40 TF/s on the generic kernel); because Cin
-// is tiny the im2col matrix itself is cheap - [B*OH*OW][KP] is 2.5x the convolution's OUTPUT - and turns both the forward and
-// the weight gradient (which re-reads the same matrix) into plain tuned GEMMs.  KP = K rounded up to the GEMM's k-tile,
-// zero-filled, as are the taps that fall into the padding.
+// 147 / 98 the implicit-GEMM gather spends its time on per-element tap arithmetic (40 TF/s on the generic kernel); the explicit
+// matrix turns both the forward and the weight gradient (which re-reads the same matrix) into plain tuned GEMMs.  It is not
+// cheap: [B*OH*OW][KP] is 2.5x / 1.75x the convolution's OUTPUT (336 / 235 MB at B = 32), written once and read twice per step -
+// 73 us for this kernel next to 116 us for the GEMM that consumes it (profiles/r06_graph_timeline.txt), all of it HBM streaming.
+// A convolution that forms the patch tile in LDS would remove it; until one exists this is the stems' largest remaining stream
+// (their other one, the stem-resolution activation and its gradient, is gone: norm.hip, stem_bn_relu_maxpool_kernel).
+// KP = K rounded up to the GEMM's k-tile, zero-filled, as are the taps that fall into the padding.
 namespace {
 // One thread per (output pixel, 4 consecutive k): the tap of every k - its offset inside the image and its (kh, kw) for the padding
 // test - comes from a per-block LDS table (K <= 256 entries, built once per block), the pixel from a multiply-high by the host's

@@ -827,3 +827,217 @@ extern "C" int mmfn_colsum_f32(const float* in, int64_t M, int C, int ld, float*
 extern "C" int mmfn_colsum_bf16(const void* in, int64_t M, int C, int ld, float* out, void* workspace, void* stream) {
   return colsum_batched_launch((const bf16_t*)in, 1, 0, M, C, ld, out, 0, workspace, stream);
 }
+
+// ------------------------------------------------------------------ the 7x7 stems: BatchNorm + ReLU + maxpool without y and gy
+// The stem's activation y = relu(bn(co)) [B,H,W,C] is the largest tensor of the network and only ever feeds MaxPool2d(3,2,1);
+// its gradient gy is only ever produced by that pooling's backward.  Neither has to exist in HBM:
+//   forward : pooled / idx straight from co (bn_apply_kernel<false,true> + maxpool_fwd_kernel in one pass),
+//   backward: the BatchNorm backward's loaders form gy from the pooled gradient and the argmax taps (maxpool_bwd_kernel's gather)
+//             and the ReLU sign from co (MASK == 2 above).
+// Same expressions, comparison order, row partition and combine order as the kernels they replace: every output is bit-identical.
+namespace {
+
+// bn_apply_kernel<false, true>'s value of one stem pixel, then maxpool_fwd_kernel (pool.hip): taps in kh / kw order, first
+// maximum wins, NaN propagates
+__global__ __launch_bounds__(NT) void stem_bn_relu_maxpool_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                                  uint8_t* __restrict__ idx, int B, int H, int W, int C, int OH, int OW,
+                                                                  const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                                  const float* __restrict__ w, const float* __restrict__ b) {
+  const int cq = C >> 2;
+  const int64_t total = (int64_t)B * OH * OW * cq;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int c4 = (int)(i % cq) * 4;
+    unsigned p = (unsigned)(i / cq);
+    const int ow = (int)(p % (unsigned)OW); p /= (unsigned)OW;
+    const int oh = (int)(p % (unsigned)OH);
+    const int bi_ = (int)(p / (unsigned)OH);
+    float alpha[4], beta[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { alpha[e] = mmfn_bn_alpha(w[c4 + e], rstd[c4 + e]); beta[e] = mmfn_bn_beta(b[c4 + e], mean[c4 + e], alpha[e]); }
+    f32x4 best = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    int bi[4] = {0, 0, 0, 0};
+    bool first = true;
+#pragma unroll
+    for (int kh = 0; kh < 3; ++kh) {
+      const int ih = oh * 2 - 1 + kh;
+      if ((unsigned)ih >= (unsigned)H) continue;
+#pragma unroll
+      for (int kw = 0; kw < 3; ++kw) {
+        const int iw = ow * 2 - 1 + kw;
+        if ((unsigned)iw >= (unsigned)W) continue;
+        f32x4 v = ldx4(x + ((size_t)(bi_ * H + ih) * W + iw) * C + c4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = fmaxf(mmfn_bn_affine(v[e], alpha[e], beta[e]), 0.0f);
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (first || v[e] > best[e] || v[e] != v[e]) { best[e] = v[e]; bi[e] = kh * 3 + kw; }
+        first = false;
+      }
+    }
+    stx4(y + (size_t)(i / cq) * C + c4, best);
+    uchar4 o;
+    o.x = (uint8_t)bi[0]; o.y = (uint8_t)bi[1]; o.z = (uint8_t)bi[2]; o.w = (uint8_t)bi[3];
+    *reinterpret_cast<uchar4*>(idx + (size_t)(i / cq) * C + c4) = o;
+  }
+}
+
+// gy of stem pixel (b, ih, iw), channels c4 .. c4+3: maxpool_bwd_kernel's gather (pool.hip).  The pixel lies in the windows
+// (ih >> 1 .. (ih + 1) >> 1) x (iw >> 1 .. (iw + 1) >> 1), clipped to the pooled map; they are summed oh outer, ow inner, a window
+// contributing where its argmax tap is this pixel.  The four loads are issued together (an absent window re-reads the first and
+// matches no tap).
+__device__ __forceinline__ f32x4 stem_pooled_grad(const float* __restrict__ g, const uint8_t* __restrict__ idx, int b, int ih, int iw,
+                                                  int c4, int C, int OH, int OW) {
+  const int oh0 = ih >> 1, ow0 = iw >> 1;
+  const bool two_h = (ih & 1) && oh0 + 1 < OH, two_w = (iw & 1) && ow0 + 1 < OW;
+  f32x4 gq[4];
+  uchar4 a[4];
+  int me[4];
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    const int dy = d >> 1, dx = d & 1;
+    const bool ok = (dy == 0 || two_h) && (dx == 0 || two_w);
+    const int oh = ok ? oh0 + dy : oh0, ow = ok ? ow0 + dx : ow0;
+    const size_t off = ((size_t)(b * OH + oh) * OW + ow) * C + c4;
+    a[d] = *reinterpret_cast<const uchar4*>(idx + off);
+    gq[d] = ldx4(g + off);
+    me[d] = ok ? (ih - (oh * 2 - 1)) * 3 + (iw - (ow * 2 - 1)) : 255;
+  }
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    if (a[d].x == me[d]) acc[0] += gq[d][0];
+    if (a[d].y == me[d]) acc[1] += gq[d][1];
+    if (a[d].z == me[d]) acc[2] += gq[d][2];
+    if (a[d].w == me[d]) acc[3] += gq[d][3];
+  }
+  return acc;
+}
+
+// col_partial_kernel<1, 2> with g gathered from the pooled gradient: same rows per block, same lanes, same fp64 combine
+__global__ __launch_bounds__(NT) void stem_bn_bwd_partial_kernel(const float* __restrict__ x, const float* __restrict__ gp,
+                                                                 const uint8_t* __restrict__ idx, const float* __restrict__ mean,
+                                                                 const float* __restrict__ rstd, const float* __restrict__ zw,
+                                                                 const float* __restrict__ zb, int H, int W, int OH, int OW,
+                                                                 int64_t M, int C, int64_t rows_per_block, double* __restrict__ partials) {
+  const int cq = C >> 2;
+  const int tid = threadIdx.x;
+  const int col4 = tid % cq;       // requires cq <= 256 and 256 % cq == 0
+  const int rl = tid / cq;
+  const int RL = NT / cq;
+  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+  const int64_t r1 = (r0 + rows_per_block < M) ? r0 + rows_per_block : M;
+  double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
+  f32x4 al, be;
+  const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + col4 * 4);
+  const f32x4 rs = *reinterpret_cast<const f32x4*>(rstd + col4 * 4);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { al[e] = mmfn_bn_alpha(zw[col4 * 4 + e], rs[e]); be[e] = mmfn_bn_beta(zb[col4 * 4 + e], mu[e], al[e]); }
+  for (int64_t r = r0 + rl; r < r1; r += RL) {
+    unsigned p = (unsigned)r;
+    const int iw = (int)(p % (unsigned)W); p /= (unsigned)W;
+    const int ih = (int)(p % (unsigned)H);
+    const int b = (int)(p / (unsigned)H);
+    const f32x4 xv = ldx4(x + (size_t)r * C + col4 * 4);
+    f32x4 gv = stem_pooled_grad(gp, idx, b, ih, iw, col4 * 4, C, OH, OW);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) gv[e] = mmfn_bn_affine(xv[e], al[e], be[e]) > 0.0f ? gv[e] : 0.0f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float xh = (xv[e] - mu[e]) * rs[e];
+      s1[e] += (double)gv[e];
+      s2[e] += (double)gv[e] * (double)xh;
+    }
+  }
+  __shared__ double red[2][NT][4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { red[0][tid][e] = s1[e]; red[1][tid][e] = s2[e]; }
+  __syncthreads();
+  if (rl == 0) {
+    for (int k = 1; k < RL; ++k)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { s1[e] += red[0][k * cq + col4][e]; s2[e] += red[1][k * cq + col4][e]; }
+    double* p = partials + (size_t)blockIdx.x * 2 * C;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { p[col4 * 4 + e] = s1[e]; p[C + col4 * 4 + e] = s2[e]; }
+  }
+}
+
+// bn_bwd_apply_kernel<2, false> with g gathered from the pooled gradient
+__global__ __launch_bounds__(NT) void stem_bn_bwd_apply_kernel(const float* __restrict__ gp, const uint8_t* __restrict__ idx,
+                                                               const float* __restrict__ x, float* __restrict__ dx, int H, int W, int OH,
+                                                               int OW, int64_t total4, int C, const float* __restrict__ mean,
+                                                               const float* __restrict__ rstd, const float* __restrict__ w,
+                                                               const float* __restrict__ zb, const float* __restrict__ means) {
+  const int cq = C >> 2;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (int64_t)gridDim.x * blockDim.x) {
+    const int c4 = (int)(i % cq) * 4;
+    unsigned p = (unsigned)(i / cq);
+    const int iw = (int)(p % (unsigned)W); p /= (unsigned)W;
+    const int ih = (int)(p % (unsigned)H);
+    const int b = (int)(p / (unsigned)H);
+    const f32x4 xv = ldx4(x + i * 4);
+    f32x4 gv = stem_pooled_grad(gp, idx, b, ih, iw, c4, C, OH, OW);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float alpha, beta;
+      { alpha = mmfn_bn_alpha(w[c4 + e], rstd[c4 + e]); beta = mmfn_bn_beta(zb[c4 + e], mean[c4 + e], alpha); }
+      gv[e] = mmfn_bn_affine(xv[e], alpha, beta) > 0.0f ? gv[e] : 0.0f;
+    }
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float rs = rstd[c4 + e];
+      const float xh = (xv[e] - mean[c4 + e]) * rs;
+      o[e] = (gv[e] - means[c4 + e] - xh * means[C + c4 + e]) * (w[c4 + e] * rs);
+    }
+    stx4(dx + i * 4, o);
+  }
+}
+
+// what both entries take: fp32 NHWC stem output with even extents (every 3x3/s2/p1 window starts one pixel before an even row /
+// column), channels as col_partial_kernel needs them, pixel count within the kernels' 32-bit row arithmetic
+bool stem_pool_shape_ok(int B, int H, int W, int C) {
+  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (H & 1) || (W & 1)) return false;
+  if (C % 4 || C > 1024 || (NT % (C / 4))) return false;
+  return (int64_t)B * H * W < ((int64_t)1 << 31);
+}
+}  // namespace
+
+extern "C" int mmfn_stem_pool_ok(int B, int H, int W, int C) { return stem_pool_shape_ok(B, H, W, C) ? 1 : 0; }
+
+extern "C" int mmfn_stem_bn_relu_maxpool_fwd_f32(const float* x, const float* mean, const float* rstd, const float* weight,
+                                                 const float* bias, float* y, uint8_t* idx, int B, int H, int W, int C, void* stream) {
+  if (!x || !mean || !rstd || !weight || !bias || !y || !idx || !stem_pool_shape_ok(B, H, W, C)) return MMFN_EINVAL;
+  const int OH = H / 2, OW = W / 2;
+  const int64_t total = (int64_t)B * OH * OW * (C / 4);
+  hipLaunchKernelGGL(stem_bn_relu_maxpool_kernel, dim3((int)std::min<int64_t>(ceil_div64(total, NT), 16384)), dim3(NT), 0,
+                     (hipStream_t)stream, x, y, idx, B, H, W, C, OH, OW, mean, rstd, weight, bias);
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mmfn_stem_bn_bwd_pooled_f32(const float* g, const uint8_t* idx, const float* x, int B, int H, int W, int C,
+                                           const float* mean, const float* rstd, const float* weight, const float* bias, float* dx,
+                                           float* dweight, float* dbias, void* workspace, void* stream) {
+  if (!g || !idx || !x || !mean || !rstd || !weight || !bias || !dx || !dweight || !dbias || !workspace ||
+      !stem_pool_shape_ok(B, H, W, C))
+    return MMFN_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const int OH = H / 2, OW = W / 2;
+  const int64_t M = (int64_t)B * H * W;
+  int64_t rpb;
+  const int nblk = bn_grid(M, C, &rpb);
+  double* partials = (double*)workspace;
+  float* means = (float*)(partials + (size_t)nblk * 2 * C);
+  hipLaunchKernelGGL(stem_bn_bwd_partial_kernel, dim3(nblk), dim3(NT), 0, s, x, g, idx, mean, rstd, weight, bias, H, W, OH, OW, M, C, rpb,
+                     partials);
+  MMFN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(ceil_div(C, FIN_COLS)), dim3(FIN_COLS * FIN_LANES), 0, s, partials, nblk, M, C, dweight, dbias,
+                     means);
+  MMFN_LAUNCH_CHECK();
+  const int64_t total4 = M * (C / 4);
+  hipLaunchKernelGGL(stem_bn_bwd_apply_kernel, dim3((int)std::min<int64_t>(ceil_div64(total4, NT), 8192)), dim3(NT), 0, s, g, idx, x, dx, H,
+                     W, OH, OW, total4, C, mean, rstd, weight, bias, means);
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}

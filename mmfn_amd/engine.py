@@ -232,6 +232,18 @@ class ConvBN(object):
         ops.linear_dw(dco.view(-1, Co), col, out=dwp)
         ops.repitch_rows(dwp, self.gw, Co, K, KP, K)
 
+    def bwd_pooled(self, ctx, g, idx):
+        """Backward of a stem whose BatchNorm + ReLU ran inside the pooling pass (ResNetTrunk.stem_fwd): g = dL/d(pooled), idx
+        the pooling's argmax taps.  Neither dL/d(activation) nor the activation exists; no data gradient."""
+        x, co, y, mean, rstd, relu = self.saved
+        assert relu and y is None
+        dco = ctx.bufs.get(self.name + ".dconv", co.shape)
+        ops.stem_bn_bwd_pooled(g, idx, co, mean, rstd, self.bn_w, self.bn_b, dco, self.g_bn_w, self.g_bn_b)
+        if self.is_stem():
+            self.stem_wgrad(ctx, dco)
+        else:
+            ops.conv2d_wgrad(dco, x, tuple(self.w.shape), self.stride, self.pad, out=self.gw, v=getattr(self, "saved_v", None))
+
     def fwd16(self, ctx, x, relu=True, res=None, lazy=False):
         """bf16 mode.  A trunk convolution (bf16 input): direct implicit GEMM on the bf16 MFMA pipe whose epilogue also emits
         the BatchNorm batch-statistics partial sums of its fp32 accumulators (no statistics pass over the output); a stem (fp32
@@ -536,16 +548,29 @@ class ResNetTrunk(object):
                     yield blk.down
 
     def stem_fwd(self, ctx, x):
-        y = self.stem.fwd(ctx, x, relu=True)
+        """conv1 -> bn1 -> relu -> maxpool.  fp32 path: the BatchNorm + ReLU are applied inside the pooling pass
+        (ops.stem_bn_relu_maxpool) and the stem-resolution activation is never written; a shape ops.stem_pool_ok refuses, the
+        bf16 mode and the BatchNorm-folded eval forward keep the apply and the pooling as two launches."""
+        y = self.stem.fwd(ctx, x, relu=True, lazy=not ctx.bf16)
         B, H, W, C = y.shape
+        fused = isinstance(y, PendingBN) and ops.stem_pool_ok(y.shape, y.dtype)
         p = ctx.bufs.get(self.name + ".pool", (B, (H + 1) // 2, (W + 1) // 2, C), y.dtype)
         idx = ctx.bufs.get(self.name + ".poolidx", p.shape, torch.uint8)
+        if fused:
+            st = self.stem
+            ops.stem_bn_relu_maxpool(y.co, st.saved[3], st.saved[4], st.bn_w, st.bn_b, p, idx)
+            self.pool_saved = (None, idx)
+            return p
+        y = as_tensor(ctx, y)
         ops.maxpool_fwd(y, p, idx)
         self.pool_saved = (y, idx)
         return p
 
     def stem_bwd(self, ctx, g):
         y, idx = self.pool_saved
+        if y is None:   # fused forward: the pooling's backward and the ReLU mask happen in the BatchNorm backward's loaders
+            self.stem.bwd_pooled(ctx, g, idx)
+            return
         gy = ctx.bufs.get(self.name + ".dpool", y.shape, y.dtype)
         ops.maxpool_bwd(g, idx, gy)
         self.stem.bwd(ctx, gy, need_dx=False)

@@ -917,6 +917,29 @@ def maxpool_bwd(gy, idx, gx):
     return gx
 
 
+def stem_pool_ok(co_shape, dtype=torch.float32):
+    """Do stem_bn_relu_maxpool / stem_bn_bwd_pooled take a stem whose convolution output is co_shape [B,H,W,C]?  (fp32, even
+    extents; anything else keeps bn_apply + maxpool_fwd and maxpool_bwd + bn_bwd.)"""
+    B, H, W, C = co_shape
+    return dtype == torch.float32 and lib().mmfn_stem_pool_ok(B, H, W, C) == 1
+
+
+def stem_bn_relu_maxpool(co, mean, rstd, weight, bias, pooled, idx):
+    """pooled, idx = maxpool3x3s2(relu(bn(co))) in one pass; relu(bn(co)) is never written."""
+    B, H, W, C = co.shape
+    _call("mmfn_stem_bn_relu_maxpool_fwd_f32", ptr(co), ptr(mean), ptr(rstd), ptr(weight), ptr(bias), ptr(pooled), ptr(idx), B, H, W, C,
+          stream())
+    return pooled
+
+
+def stem_bn_bwd_pooled(g, idx, co, mean, rstd, weight, bias, dco, dweight, dbias):
+    """bn_bwd of the stem fed by the POOLED gradient g [B,H/2,W/2,C]: maxpool_bwd and the ReLU mask happen in the loaders."""
+    B, H, W, C = co.shape
+    _call("mmfn_stem_bn_bwd_pooled_f32", ptr(g), ptr(idx), ptr(co), B, H, W, C, ptr(mean), ptr(rstd), ptr(weight), ptr(bias), ptr(dco),
+          ptr(dweight), ptr(dbias), ptr(norm_workspace(co.device)), stream())
+    return dco
+
+
 def _frames(frames, n):
     """Host int32[n] of frames per sample for each modality (None: one each - seq_len = n_views = 1)."""
     if frames is None:
