@@ -555,6 +555,36 @@ int mmfn_grad_accum_blocks(int64_t n);
 int mmfn_grad_norm_finalize(const double* partials, int n_partials, const float* scale, const float* max_norm, float* norm,
                             float* coef, void* stream);
 
+/* ---- non-finite guard: the optimizer step decided on the device, inside a captured hipGraph --------------------- */
+/* mmfn_grad_norm_finalize plus the decision: *ok = isfinite(*norm) (int32, 1 = take the step), *skipped += 1 when not (int64).
+ * coef and max_norm are required here.  The launches below read *ok and do nothing at all when it is 0. */
+int mmfn_grad_norm_finalize_guard(const double* partials, int n_partials, const float* scale, const float* max_norm, float* norm,
+                                  float* coef, int32_t* ok, int64_t* skipped, void* stream);
+/* *step += 1 when *ok */
+int mmfn_step_advance_if(int64_t* step, const int32_t* ok, void* stream);
+/* mmfn_adamw_groups_coef_f32 / mmfn_adamw_groups_coef_avg_f32 behind *ok: bit-identical to them when *ok, no access otherwise */
+int mmfn_adamw_groups_guard_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of, const float* hyper,
+                                int n_groups, const int64_t* step, const float* coef, const int32_t* ok, void* stream);
+int mmfn_adamw_groups_guard_avg_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of,
+                                    const float* hyper, int n_groups, const int64_t* step, const float* coef, float* avg,
+                                    const int64_t* n_averaged, const float* ema_w, int mode, const int32_t* ok, void* stream);
+/* mmfn_weight_average_f32 behind *ok */
+int mmfn_weight_average_if_f32(float* avg, const float* src, int64_t n, const int64_t* n_averaged, const float* ema_w, int mode,
+                               const int32_t* ok, void* stream);
+/* dst[0, nbytes) = src when (*flag != 0) == (when != 0), nothing otherwise.  dst, src 16-byte aligned, nbytes % 4 == 0, flag
+ * an int32 in device memory, else MMFN_EINVAL. */
+int mmfn_copy_if(void* dst, const void* src, int64_t nbytes, const int32_t* flag, int when, void* stream);
+
+/* ---- per-tensor statistics of a flat buffer ---------------------------------------------------------------------- */
+/* table: int64 [n_tensors][3] in device memory = (offset, count, first chunk) per tensor, offsets multiples of 4 floats, a tensor
+ * of count floats owning ceil(count / mmfn_tensor_stats_chunk()) consecutive chunks, n_chunks in all.  out: fp64 [n_tensors][3] =
+ * (|scale| * L2 norm over all entries, |scale| * max |x| over the finite entries (0 without any), count of non-finite entries).
+ * workspace: 3 * n_chunks fp64.  Reads exactly `count` floats per tensor; fixed slots and summation order, so two calls on the
+ * same data return the same bits.  flat 16-byte aligned, the others 8, else MMFN_EINVAL. */
+int mmfn_tensor_stats_chunk(void);
+int mmfn_tensor_stats_f32(const float* flat, const int64_t* table, int n_tensors, int64_t n_chunks, float scale, double* out,
+                          double* workspace, void* stream);
+
 /* ---- sensor ingest (dataloader.py:271-308, model_vec.py:33-44,368-381) ------------------------- */
 int mmfn_ingest_rgb_u8(const uint8_t* in, float* out, int B, int H, int W, int crop, void* stream);
 int mmfn_nchw_to_nhwc_f32(const float* in, float* out, int B, int C, int P, const float* mean, const float* inv_std,

@@ -64,14 +64,20 @@ class AveragedMMFN(object):
         if L.offsets is not A.offsets and (L.total != A.total or L.offsets != A.offsets):
             raise ValueError("model and average have different flat layouts (another variant or config?)")
 
-    def update_buffers(self, model):
-        """BatchNorm running statistics: averaged (use_buffers) or copied; the int64 counters copied."""
+    def update_buffers(self, model, ok=None):
+        """BatchNorm running statistics: averaged (use_buffers) or copied; the int64 counters copied.  ok: the non-finite guard's
+        device flag (Engine.final_adam): nothing changes when it is 0."""
         L, A = model._layout, self.module._layout
         if self.use_buffers:
-            ops.weight_average(A.buffers_flat, L.buffers_flat, self.n_averaged, self.ema_weight, self.mode_code)
-        else:
+            ops.weight_average(A.buffers_flat, L.buffers_flat, self.n_averaged, self.ema_weight, self.mode_code, ok=ok)
+        elif ok is None:
             A.buffers_flat.copy_(L.buffers_flat)
-        A.counters_flat.copy_(L.counters_flat)
+        else:
+            ops.copy_if(A.buffers_flat, L.buffers_flat, ok, when=True)
+        if ok is None:
+            A.counters_flat.copy_(L.counters_flat)
+        else:
+            ops.copy_if(A.counters_flat, L.counters_flat, ok, when=True)
 
     def update_parameters(self, model):
         """AveragedModel.update_parameters: average every parameter of `model` into the copy (the never-trained tail included:

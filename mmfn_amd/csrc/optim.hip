@@ -8,6 +8,9 @@
 
 namespace {
 __global__ void step_advance_kernel(int64_t* step) { *step += 1; }
+__global__ void step_advance_if_kernel(int64_t* step, const int32_t* ok) {
+  if (*ok) *step += 1;
+}
 
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, int64_t n, float lr, float beta1, float beta2,
@@ -52,6 +55,13 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
 
 extern "C" int mmfn_step_advance(int64_t* step, void* stream) {
   hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step);
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mmfn_step_advance_if(int64_t* step, const int32_t* ok, void* stream) {
+  if (!step || ((uintptr_t)step & 7) || !ok || ((uintptr_t)ok & 3)) return MMFN_EINVAL;
+  hipLaunchKernelGGL(step_advance_if_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step, ok);
   MMFN_LAUNCH_CHECK();
   return 0;
 }
@@ -106,13 +116,16 @@ __device__ inline f32x4 lerp4(f32x4 a, f32x4 p, float w) {
 
 // COEF: every group's grad_scale is multiplied by *coef (the clip_grad_norm_ coefficient, written on the device by
 // mmfn_grad_norm_finalize); COEF = false is the plain grouped step.  AVG: the new parameter is also folded into avg.avg
-// (the weight average), from registers: 8 B more per parameter instead of a 12 B pass of its own
-template <bool COEF, bool AVG>
+// (the weight average), from registers: 8 B more per parameter instead of a 12 B pass of its own.  GUARD (with COEF only): *ok
+// is the non-finite guard's flag (mmfn_grad_norm_finalize_guard); when it is 0 the whole grid returns before it reads or writes
+// anything, so parameters, moments and the average keep their bits
+template <bool COEF, bool AVG, bool GUARD>
 __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                            float* __restrict__ v, int64_t n, const uint8_t* __restrict__ group_of,
                                                            const float* __restrict__ hyper, int n_groups,
                                                            const int64_t* __restrict__ step, const float* __restrict__ coef,
-                                                           AvgArgs avg) {
+                                                           AvgArgs avg, const int32_t* __restrict__ ok) {
+  if (GUARD && !*ok) return;   // uniform over the grid: no barrier is left behind
   __shared__ GroupScalars gs[MMFN_ADAMW_MAX_GROUPS];
   if ((int)threadIdx.x < n_groups) {
     const float* h = hyper + threadIdx.x * 8;
@@ -157,7 +170,10 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p
   }
 }
 
-__global__ __launch_bounds__(256) void weight_average_kernel(const float* __restrict__ src, int64_t n4, AvgArgs avg) {
+template <bool GUARD>
+__global__ __launch_bounds__(256) void weight_average_kernel(const float* __restrict__ src, int64_t n4, AvgArgs avg,
+                                                             const int32_t* __restrict__ ok) {
+  if (GUARD && !*ok) return;
   const bool copy = *avg.n_averaged == 0;
   const float w = copy ? 1.0f : avg_weight(avg);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
@@ -189,8 +205,8 @@ extern "C" int mmfn_adamw_groups_f32(float* p, const float* g, float* m, float* 
       (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15))
     return MMFN_EINVAL;
   const int blocks = (int)std::min<int64_t>(ceil_div64(n / 4, 256), 4096);
-  hipLaunchKernelGGL((adamw_groups_kernel<false, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, group_of,
-                     hyper, n_groups, step, (const float*)nullptr, AvgArgs{});
+  hipLaunchKernelGGL((adamw_groups_kernel<false, false, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, group_of,
+                     hyper, n_groups, step, (const float*)nullptr, AvgArgs{}, (const int32_t*)nullptr);
   MMFN_LAUNCH_CHECK();
   return 0;
 }
@@ -202,8 +218,8 @@ extern "C" int mmfn_adamw_groups_coef_f32(float* p, const float* g, float* m, fl
       (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15))
     return MMFN_EINVAL;
   const int blocks = (int)std::min<int64_t>(ceil_div64(n / 4, 256), 4096);
-  hipLaunchKernelGGL((adamw_groups_kernel<true, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, group_of,
-                     hyper, n_groups, step, coef, AvgArgs{});
+  hipLaunchKernelGGL((adamw_groups_kernel<true, false, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, group_of,
+                     hyper, n_groups, step, coef, AvgArgs{}, (const int32_t*)nullptr);
   MMFN_LAUNCH_CHECK();
   return 0;
 }
@@ -214,8 +230,8 @@ extern "C" int mmfn_adamw_groups_avg_f32(float* p, const float* g, float* m, flo
   if (n <= 0) return 0;
   const AvgArgs a{avg, n_averaged, ema_w, mode};
   if (!adamw_args_ok(p, g, m, v, n, hyper, n_groups, step) || !avg_args_ok(a)) return MMFN_EINVAL;
-  hipLaunchKernelGGL((adamw_groups_kernel<false, true>), dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
-                     group_of, hyper, n_groups, step, (const float*)nullptr, a);
+  hipLaunchKernelGGL((adamw_groups_kernel<false, true, false>), dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
+                     group_of, hyper, n_groups, step, (const float*)nullptr, a, (const int32_t*)nullptr);
   MMFN_LAUNCH_CHECK();
   return 0;
 }
@@ -226,8 +242,8 @@ extern "C" int mmfn_adamw_groups_coef_avg_f32(float* p, const float* g, float* m
   if (n <= 0) return 0;
   const AvgArgs a{avg, n_averaged, ema_w, mode};
   if (!coef || !adamw_args_ok(p, g, m, v, n, hyper, n_groups, step) || !avg_args_ok(a)) return MMFN_EINVAL;
-  hipLaunchKernelGGL((adamw_groups_kernel<true, true>), dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
-                     group_of, hyper, n_groups, step, coef, a);
+  hipLaunchKernelGGL((adamw_groups_kernel<true, true, false>), dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
+                     group_of, hyper, n_groups, step, coef, a, (const int32_t*)nullptr);
   MMFN_LAUNCH_CHECK();
   return 0;
 }
@@ -237,7 +253,73 @@ extern "C" int mmfn_weight_average_f32(float* avg, const float* src, int64_t n, 
   if (n <= 0) return 0;
   const AvgArgs a{avg, n_averaged, ema_w, mode};
   if (!src || ((uintptr_t)src & 15) || (n & 3) || !avg_args_ok(a)) return MMFN_EINVAL;
-  hipLaunchKernelGGL(weight_average_kernel, dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, src, n / 4, a);
+  hipLaunchKernelGGL(weight_average_kernel<false>, dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, src, n / 4, a,
+                     (const int32_t*)nullptr);
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- the non-finite guard's forms: the same launches behind the device flag *ok (1 = take the step, 0 = skip it) -------------
+namespace {
+bool flag_ok(const int32_t* ok) { return ok && !((uintptr_t)ok & 3); }
+}  // namespace
+
+extern "C" int mmfn_adamw_groups_guard_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of,
+                                           const float* hyper, int n_groups, const int64_t* step, const float* coef, const int32_t* ok,
+                                           void* stream) {
+  if (n <= 0) return 0;
+  if (!coef || !flag_ok(ok) || !adamw_args_ok(p, g, m, v, n, hyper, n_groups, step)) return MMFN_EINVAL;
+  hipLaunchKernelGGL((adamw_groups_kernel<true, false, true>), dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
+                     group_of, hyper, n_groups, step, coef, AvgArgs{}, ok);
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mmfn_adamw_groups_guard_avg_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of,
+                                               const float* hyper, int n_groups, const int64_t* step, const float* coef, float* avg,
+                                               const int64_t* n_averaged, const float* ema_w, int mode, const int32_t* ok,
+                                               void* stream) {
+  if (n <= 0) return 0;
+  const AvgArgs a{avg, n_averaged, ema_w, mode};
+  if (!coef || !flag_ok(ok) || !adamw_args_ok(p, g, m, v, n, hyper, n_groups, step) || !avg_args_ok(a)) return MMFN_EINVAL;
+  hipLaunchKernelGGL((adamw_groups_kernel<true, true, true>), dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
+                     group_of, hyper, n_groups, step, coef, a, ok);
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mmfn_weight_average_if_f32(float* avg, const float* src, int64_t n, const int64_t* n_averaged, const float* ema_w,
+                                          int mode, const int32_t* ok, void* stream) {
+  if (n <= 0) return 0;
+  const AvgArgs a{avg, n_averaged, ema_w, mode};
+  if (!src || ((uintptr_t)src & 15) || (n & 3) || !flag_ok(ok) || !avg_args_ok(a)) return MMFN_EINVAL;
+  hipLaunchKernelGGL(weight_average_kernel<true>, dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, src, n / 4, a, ok);
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
+
+// dst = src over nbytes when (*flag != 0) == (when != 0), else nothing: the guard's rollback of the BatchNorm state (when = 0)
+// and the gated copies of an attached average's buffers (when = 1).  16-byte body, 4-byte tail.
+namespace {
+__global__ __launch_bounds__(256) void copy_if_kernel(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src, int64_t n_words,
+                                                      const int32_t* __restrict__ flag, int when) {
+  if ((*flag != 0) != (when != 0)) return;
+  const int64_t n4 = n_words >> 2;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (int64_t i = tid; i < n4; i += (int64_t)gridDim.x * blockDim.x)
+    reinterpret_cast<uint4*>(dst)[i] = reinterpret_cast<const uint4*>(src)[i];
+  const int64_t t = n4 * 4 + tid;
+  if (t < n_words) dst[t] = src[t];
+}
+}  // namespace
+
+extern "C" int mmfn_copy_if(void* dst, const void* src, int64_t nbytes, const int32_t* flag, int when, void* stream) {
+  if (nbytes <= 0) return 0;
+  if (!dst || !src || (((uintptr_t)dst | (uintptr_t)src) & 15) || (nbytes & 3) || !flag_ok(flag)) return MMFN_EINVAL;
+  const int64_t n_words = nbytes / 4;
+  const int blocks = (int)std::min<int64_t>(ceil_div64(n_words / 4 + 4, 256), 1024);
+  hipLaunchKernelGGL(copy_if_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (uint32_t*)dst, (const uint32_t*)src, n_words,
+                     flag, when);
   MMFN_LAUNCH_CHECK();
   return 0;
 }
@@ -303,11 +385,16 @@ void launch_accum(float* g, float* acc, int64_t n, double* partials, hipStream_t
     hipLaunchKernelGGL((grad_accum_kernel<MODE, false>), dim3(blocks), dim3(kAccumThreads), 0, st, g, acc, n / 4, partials);
 }
 
-// one workgroup: the partials table summed in a fixed order (strided per thread, then the fixed block sum), norm = scale * sqrt
+__device__ inline bool finite_f32(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+
+// one workgroup: the partials table summed in a fixed order (strided per thread, then the fixed block sum), norm = scale * sqrt.
+// GUARD: *ok = isfinite(norm) and *skipped += !ok, plain stores from lane 0 (the non-finite guard: the launches behind it read *ok)
+template <bool GUARD>
 __global__ __launch_bounds__(kAccumThreads) void grad_norm_finalize_kernel(const double* __restrict__ partials, int n,
                                                                            const float* __restrict__ scale,
                                                                            const float* __restrict__ max_norm,
-                                                                           float* __restrict__ norm, float* __restrict__ coef) {
+                                                                           float* __restrict__ norm, float* __restrict__ coef,
+                                                                           int32_t* __restrict__ ok, int64_t* __restrict__ skipped) {
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += kAccumThreads) s += partials[i];
   const double t = block_sum_f64(s);
@@ -318,6 +405,11 @@ __global__ __launch_bounds__(kAccumThreads) void grad_norm_finalize_kernel(const
       // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max=1); a NaN norm propagates into the step
       const float c = *max_norm / (nrm + 1e-6f);
       *coef = c > 1.0f ? 1.0f : c;
+    }
+    if (GUARD) {
+      const bool good = finite_f32(nrm);
+      *ok = good ? 1 : 0;
+      if (!good) *skipped += 1;
     }
   }
 }
@@ -347,8 +439,124 @@ extern "C" int mmfn_grad_accum_f32(float* g, float* acc, int64_t n, int mode, do
 extern "C" int mmfn_grad_norm_finalize(const double* partials, int n_partials, const float* scale, const float* max_norm,
                                        float* norm, float* coef, void* stream) {
   if (!partials || n_partials < 1 || !scale || !norm || (coef && !max_norm)) return MMFN_EINVAL;
-  hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(kAccumThreads), 0, (hipStream_t)stream, partials, n_partials, scale,
-                     max_norm, norm, coef);
+  hipLaunchKernelGGL(grad_norm_finalize_kernel<false>, dim3(1), dim3(kAccumThreads), 0, (hipStream_t)stream, partials, n_partials,
+                     scale, max_norm, norm, coef, (int32_t*)nullptr, (int64_t*)nullptr);
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mmfn_grad_norm_finalize_guard(const double* partials, int n_partials, const float* scale, const float* max_norm,
+                                             float* norm, float* coef, int32_t* ok, int64_t* skipped, void* stream) {
+  if (!partials || ((uintptr_t)partials & 7) || n_partials < 1 || !scale || !norm || !coef || !max_norm || !ok ||
+      ((uintptr_t)ok & 3) || !skipped || ((uintptr_t)skipped & 7))
+    return MMFN_EINVAL;
+  hipLaunchKernelGGL(grad_norm_finalize_kernel<true>, dim3(1), dim3(kAccumThreads), 0, (hipStream_t)stream, partials, n_partials,
+                     scale, max_norm, norm, coef, ok, skipped);
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- per-tensor statistics of a flat buffer: a segmented reduction in two launches ----------------------------------------------
+// Tensors hold 2 .. 2.4 M floats, so every tensor is cut into chunks of kStatsChunk floats and one workgroup reduces one chunk
+// into its own fp64 slot triple (sum of squares, max |x| over the finite entries, count of non-finite entries); a second launch
+// combines each tensor's slots.  Slots and summation order depend on the table only: two calls on the same data agree bit for bit.
+// table: int64 [n_tensors][3] = (offset, count, first chunk), offsets 16-byte aligned; entries past `count` are never read.
+namespace {
+constexpr int kStatsChunk = 16 * kAccumThreads;   // 4096 floats: four float4 per lane
+
+struct Stats3 { double sumsq, maxabs, bad; };
+
+__device__ inline void stats_add(Stats3& s, float x) {
+  if (finite_f32(x)) s.maxabs = fmax(s.maxabs, (double)fabsf(x));
+  else s.bad += 1.0;
+  s.sumsq += (double)x * (double)x;   // (a non-finite entry makes the sum non-finite)
+}
+
+// fixed-order block reduction of the triple: 64-lane butterfly, then the four waves in wave order; the result is lane 0's
+__device__ inline Stats3 block_stats(Stats3 s) {
+  __shared__ double w3[kAccumThreads / 64][3];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    s.sumsq += __shfl_xor(s.sumsq, off, 64);
+    s.maxabs = fmax(s.maxabs, __shfl_xor(s.maxabs, off, 64));
+    s.bad += __shfl_xor(s.bad, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    w3[threadIdx.x >> 6][0] = s.sumsq; w3[threadIdx.x >> 6][1] = s.maxabs; w3[threadIdx.x >> 6][2] = s.bad;
+  }
+  __syncthreads();
+  Stats3 t{0.0, 0.0, 0.0};
+  if (threadIdx.x == 0)
+    for (int w = 0; w < kAccumThreads / 64; ++w) {
+      t.sumsq += w3[w][0]; t.maxabs = fmax(t.maxabs, w3[w][1]); t.bad += w3[w][2];
+    }
+  return t;
+}
+
+__global__ __launch_bounds__(kAccumThreads) void tensor_stats_chunk_kernel(const float* __restrict__ flat,
+                                                                           const int64_t* __restrict__ table, int n_tensors,
+                                                                           double* __restrict__ slots) {
+  // the tensor whose chunk range holds this workgroup: the last one with first chunk <= blockIdx.x (uniform binary search)
+  const int64_t c = blockIdx.x;
+  int lo = 0, hi = n_tensors - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (table[mid * 3 + 2] <= c) lo = mid; else hi = mid - 1;
+  }
+  const int64_t count = table[lo * 3 + 1];
+  const int64_t base = (c - table[lo * 3 + 2]) * kStatsChunk;   // first element of the chunk inside the tensor
+  const float* x = flat + table[lo * 3 + 0];
+  Stats3 s{0.0, 0.0, 0.0};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int64_t i = base + ((int64_t)j * kAccumThreads + threadIdx.x) * 4;
+    if (i + 4 <= count) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(x + i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) stats_add(s, v[e]);
+    } else {
+      for (int64_t e = i; e < count; ++e) stats_add(s, x[e]);
+    }
+  }
+  const Stats3 t = block_stats(s);
+  if (threadIdx.x == 0) {
+    slots[c * 3 + 0] = t.sumsq; slots[c * 3 + 1] = t.maxabs; slots[c * 3 + 2] = t.bad;
+  }
+}
+
+// one workgroup per tensor: its chunk slots strided over the lanes, then the fixed block reduction
+__global__ __launch_bounds__(kAccumThreads) void tensor_stats_combine_kernel(const int64_t* __restrict__ table, int64_t n_chunks,
+                                                                             const double* __restrict__ slots, float scale,
+                                                                             double* __restrict__ out) {
+  const int t = blockIdx.x;
+  const int64_t first = table[t * 3 + 2];
+  const int64_t last = t + 1 < (int)gridDim.x ? table[(t + 1) * 3 + 2] : n_chunks;
+  Stats3 s{0.0, 0.0, 0.0};
+  for (int64_t c = first + threadIdx.x; c < last; c += kAccumThreads) {
+    s.sumsq += slots[c * 3 + 0];
+    s.maxabs = fmax(s.maxabs, slots[c * 3 + 1]);
+    s.bad += slots[c * 3 + 2];
+  }
+  const Stats3 r = block_stats(s);
+  if (threadIdx.x == 0) {
+    const double a = fabs((double)scale);
+    out[t * 3 + 0] = a * sqrt(r.sumsq);
+    out[t * 3 + 1] = a * r.maxabs;
+    out[t * 3 + 2] = r.bad;
+  }
+}
+}  // namespace
+
+extern "C" int mmfn_tensor_stats_chunk(void) { return kStatsChunk; }
+
+extern "C" int mmfn_tensor_stats_f32(const float* flat, const int64_t* table, int n_tensors, int64_t n_chunks, float scale,
+                                     double* out, double* workspace, void* stream) {
+  if (!flat || ((uintptr_t)flat & 15) || !table || ((uintptr_t)table & 7) || !out || ((uintptr_t)out & 7) || !workspace ||
+      ((uintptr_t)workspace & 7) || n_tensors < 1 || n_chunks < n_tensors || n_chunks > 0x7fffffff)
+    return MMFN_EINVAL;
+  const hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(tensor_stats_chunk_kernel, dim3((unsigned)n_chunks), dim3(kAccumThreads), 0, st, flat, table, n_tensors, workspace);
+  hipLaunchKernelGGL(tensor_stats_combine_kernel, dim3(n_tensors), dim3(kAccumThreads), 0, st, table, n_chunks, workspace, scale, out);
   MMFN_LAUNCH_CHECK();
   return 0;
 }

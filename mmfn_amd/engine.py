@@ -1434,6 +1434,9 @@ class Engine(object):
         self._norm = None           # partials table, its slots, and the device (norm, coef) pair
         self._tiling_checked = False
         self.average = None         # averaging.AveragedMMFN updated inside every optimizer step's AdamW launch (attach_average)
+        self.nonfinite_guard = False   # set_nonfinite_guard: skip an optimizer step whose gradient norm is not finite
+        self._guard = None          # its device flag, skip counter and BatchNorm shadows (allocated when first armed)
+        self._stats_tab = None      # tensor_stats: the device table of the layout's tensors
         self.n_lanes = int(os.environ.get("MMFN_BRANCH_LANES", "3"))
         self.offload_wgrad = True   # transformer weight / bias gradients on the side stream (worth 3.9 ms per step)
 
@@ -1837,15 +1840,74 @@ class Engine(object):
     def detach_average(self):
         self.average = None
 
-    def _adamw_average(self, n_groups, group_of, coef=None):
+    def _adamw_average(self, n_groups, group_of, coef=None, ok=None):
         """The AdamW launch with the attached average folded in (coef: the clipping instance), then the average's BatchNorm
-        buffers and its count: three launches (+ a counter copy) instead of one."""
+        buffers and its count: three launches (+ a counter copy) instead of one.  ok: the non-finite guard's flag, every one of
+        them behind it."""
         L, a = self.layout, self.average
         ops.adamw_groups_avg(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self.step_count, self.opt_hyper, n_groups,
-                             a.module._layout.params, a.n_averaged, a.ema_weight, a.mode_code, group_of=group_of, coef=coef, n=L.tail)
-        a.update_buffers(self.module)
-        ops.step_advance(a.n_averaged)
+                             a.module._layout.params, a.n_averaged, a.ema_weight, a.mode_code, group_of=group_of, coef=coef, n=L.tail,
+                             ok=ok)
+        a.update_buffers(self.module, ok=ok)
+        if ok is None:
+            ops.step_advance(a.n_averaged)
+        else:
+            ops.step_advance_if(a.n_averaged, ok)
         a.module.weights_changed()
+
+    # ------------------------------------------------------------------ non-finite guard
+    def set_nonfinite_guard(self, on=True):
+        """Armed: every optimizer step of the fused path (train_step, the replayed "final" step, data parallel) measures the
+        global gradient norm (the clipped route, max_norm = inf unless the caller clips) and decides ON THE DEVICE whether to
+        take the step: a non-finite norm leaves parameters, moments, step_count and an attached average bit-identical, restores
+        the BatchNorm running statistics and counters of the start of the accumulation group, clears the accumulator and counts
+        the step in skipped_steps; a finite norm gives the unguarded step bit for bit.  rng_state advances either way.  The guard
+        keys on the gradient, not the loss (a non-finite label can leave the gradient finite), and does not cover a direct
+        optimizer_step().  A captured step records the arming and refuses to replay after it changed (parallel.GraphedStep)."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("set_nonfinite_guard() inside a hipGraph capture")
+        if on and self._guard is None:
+            L, dev = self.layout, self.device
+            self._guard = {"ok": torch.ones(1, dtype=torch.int32, device=dev), "skipped": torch.zeros(1, dtype=torch.int64, device=dev),
+                           "buffers": torch.zeros_like(L.buffers_flat), "counters": torch.zeros_like(L.counters_flat)}
+            self._norm_state()
+        self.nonfinite_guard = bool(on)
+
+    @property
+    def skipped_steps(self):
+        """Device int64 [1]: optimizer steps the guard has skipped (None before it was first armed)."""
+        return None if self._guard is None else self._guard["skipped"]
+
+    def guarded_clip(self, clip_grad_norm):
+        """max_norm of an optimizer step: the caller's, or inf while the guard is armed (its decision needs the norm)."""
+        return float("inf") if clip_grad_norm is None and self.nonfinite_guard else clip_grad_norm
+
+    def guard_snapshot(self):
+        """BatchNorm running statistics and counters as the first micro-step of a group finds them: two device copies, issued
+        in front of that step (outside a captured graph), restored by final_adam when the step is skipped."""
+        if self.nonfinite_guard and self.accum_pending == 0:
+            L, G = self.layout, self._guard
+            G["buffers"].copy_(L.buffers_flat)
+            G["counters"].copy_(L.counters_flat)
+
+    def tensor_stats(self, which="grads"):
+        """(names, float64 [n, 3] device tensor): per trained tensor, in layout order, the L2 norm over all entries (non-finite if
+        any entry is), max |x| over the finite entries and the count of non-finite entries of the gradient ("grads": the
+        averaged gradient the last optimizer step saw - the buffer times that step's grad_scale, without the clip coefficient,
+        what last_grad_norm measures) or the parameters ("params").  One read-only pass, on demand, no host sync."""
+        if which not in ("grads", "params"):
+            raise ValueError("which must be 'grads' or 'params', got %r" % (which,))
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("tensor_stats() inside a hipGraph capture")
+        L = self.layout
+        if self._stats_tab is None:
+            names = [n for n in L.offsets if n not in L.unused]
+            self._stats_tab = (names, ops.tensor_stats_table([L.offsets[n] for n in names], self.device))
+        names, tab = self._stats_tab
+        scale = 1.0
+        if which == "grads" and self._hyper_host:
+            scale = self._hyper_host[0][5]
+        return list(names), ops.tensor_stats(L.grads if which == "grads" else L.params, tab, scale)
 
     def backward_and_step(self, dp=None, lr=1e-4, **adam):
         """Backward of the last training forward + AdamW (+ the gradient all-reduces of `dp`, issued from the streams that
@@ -1868,7 +1930,10 @@ class Engine(object):
         After accumulate_step() calls this is the last micro-step of the group: the pending sum is folded into this
         backward's gradient and AdamW sees 1 / ((pending + 1) * world) of it.  clip_grad_norm = max_norm: the step is clipped
         as torch.nn.utils.clip_grad_norm_ over every trained parameter (the norm of the averaged gradient; inf = only measure
-        it), the norm is left in last_grad_norm.  With neither, the launch sequence is the plain step's."""
+        it), the norm is left in last_grad_norm.  With neither, the launch sequence is the plain step's.  With the non-finite
+        guard armed (set_nonfinite_guard) the step always takes the clipped route and may be skipped on the device."""
+        self.guard_snapshot()
+        clip_grad_norm = self.guarded_clip(clip_grad_norm)
         ops.rng_advance(self.rng_state)
         _, loss = self.forward(inp, True, gt)
         if self.accum_pending == 0 and clip_grad_norm is None:
@@ -1886,6 +1951,7 @@ class Engine(object):
         loop), L1 loss, backward, and acc += gradient per readiness group on the stream that wrote it.  No collective, no AdamW:
         the next train_step() folds the sum in.  Returns the device loss."""
         self._accum_buffer()
+        self.guard_snapshot()
         ops.rng_advance(self.rng_state)
         _, loss = self.forward(inp, True, gt)
         self.backward_groups(ops.ACCUM_ADD, None, False)
@@ -2002,10 +2068,15 @@ class Engine(object):
     def final_adam(self, dp, clip, n_groups):
         """AdamW after backward_groups, reading the hyper table as set (final_rows); clip: global norm of the scaled
         gradient (group partials on one GPU, one read-only pass over [0, tail) after the reduction with dp), the coefficient,
-        and the coefficient AdamW.  Resets the pending count."""
+        and the coefficient AdamW.  Resets the pending count.  Guard armed: the finalize also writes the flag, and the step
+        count, the BatchNorm rollback, AdamW and the average's update all sit behind it."""
         L = self.layout
+        guard = self._guard if self.nonfinite_guard else None
+        if guard is not None and not clip:
+            raise RuntimeError("the non-finite guard decides on the gradient norm: its optimizer step is the clipped one")
         self.module.weights_changed()
-        ops.step_advance(self.step_count)
+        if guard is None:
+            ops.step_advance(self.step_count)
         group_of = self.opt_group_of if n_groups > 1 else None
         if clip:
             nm = self._norm_state()
@@ -2016,12 +2087,21 @@ class Engine(object):
             else:
                 part = nm["partials"][:nm["n_group_slots"]]
             out = nm["out"]
-            ops.grad_norm_finalize(part, self.opt_hyper[0, 5:6], self.opt_hyper[0, 6:7], out[0:1], out[1:2])
+            ok = None
+            if guard is None:
+                ops.grad_norm_finalize(part, self.opt_hyper[0, 5:6], self.opt_hyper[0, 6:7], out[0:1], out[1:2])
+            else:
+                ok = guard["ok"]
+                ops.grad_norm_finalize_guard(part, self.opt_hyper[0, 5:6], self.opt_hyper[0, 6:7], out[0:1], out[1:2], ok,
+                                             guard["skipped"])
+                ops.step_advance_if(self.step_count, ok)
+                ops.copy_if(L.buffers_flat, guard["buffers"], ok, when=False)    # skipped: the group's BatchNorm updates go
+                ops.copy_if(L.counters_flat, guard["counters"], ok, when=False)
             if self.average is not None:
-                self._adamw_average(n_groups, group_of, coef=out[1:2])
+                self._adamw_average(n_groups, group_of, coef=out[1:2], ok=ok)
             else:
                 ops.adamw_groups_coef(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self.step_count, self.opt_hyper, n_groups, out[1:2],
-                                      group_of=group_of, n=L.tail)
+                                      group_of=group_of, n=L.tail, ok=ok)
         elif self.average is not None:
             self._adamw_average(n_groups, group_of)
         else:

@@ -196,6 +196,16 @@ class MMFN(nn.Module):
         else:
             eng.attach_average(average)
 
+    def guard_nonfinite(self, on=True):
+        """Skip, on the device, every optimizer step of the fused path whose gradient norm is not finite: weights, moments,
+        BatchNorm statistics and an attached average stay as they were (engine.Engine.set_nonfinite_guard); False disarms."""
+        self._engine_for().set_nonfinite_guard(on)
+
+    def tensor_stats(self, which="grads"):
+        """(names, float64 [n, 3] device tensor of L2 norm, max |x| over the finite entries, non-finite count) per trained tensor of
+        the last step's gradient ("grads") or of the parameters ("params"): engine.Engine.tensor_stats."""
+        return self._engine_for().tensor_stats(which)
+
     # ------------------------------------------------------------------ PID (model_vec.py:684-726)
     def control_pid(self, waypoints, velocity):
         assert waypoints.size(0) == 1

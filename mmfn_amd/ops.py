@@ -1135,6 +1135,11 @@ def step_advance(step):
     _call("mmfn_step_advance", ptr(step), stream())
 
 
+def step_advance_if(step, ok):
+    """step += 1 when the device flag `ok` (int32) is set."""
+    _call("mmfn_step_advance_if", ptr(step), ptr(ok), stream())
+
+
 def rng_advance(state):
     _call("mmfn_rng_advance", ptr(state), stream())
 
@@ -1151,9 +1156,14 @@ def adamw_groups(p, g, m, v, step, hyper, n_groups, group_of=None, n=None):
     _call("mmfn_adamw_groups_f32", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(group_of), ptr(hyper), n_groups, ptr(step), stream())
 
 
-def adamw_groups_coef(p, g, m, v, step, hyper, n_groups, coef, group_of=None, n=None):
-    """adamw_groups with every group's grad_scale multiplied by the device scalar `coef` (the clip coefficient)."""
+def adamw_groups_coef(p, g, m, v, step, hyper, n_groups, coef, group_of=None, n=None, ok=None):
+    """adamw_groups with every group's grad_scale multiplied by the device scalar `coef` (the clip coefficient).  ok: the
+    non-finite guard's device flag (int32): the launch touches nothing when it is 0."""
     n = p.numel() if n is None else n
+    if ok is not None:
+        _call("mmfn_adamw_groups_guard_f32", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(group_of), ptr(hyper), n_groups, ptr(step),
+              ptr(coef), ptr(ok), stream())
+        return
     _call("mmfn_adamw_groups_coef_f32", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(group_of), ptr(hyper), n_groups, ptr(step), ptr(coef),
           stream())
 
@@ -1161,19 +1171,31 @@ def adamw_groups_coef(p, g, m, v, step, hyper, n_groups, coef, group_of=None, n=
 AVG_EMA, AVG_SWA = 0, 1   # mirror include/mmfn_hip.h
 
 
-def weight_average(avg, src, n_averaged, ema_weight, mode):
+def weight_average(avg, src, n_averaged, ema_weight, mode, ok=None):
     """avg = src (first update: *n_averaged == 0) or ATen's lerp(avg, src, w) over avg.numel() floats; w = *ema_weight (EMA) or
-    1 / (*n_averaged + 1) (SWA), both read on the device.  Does not advance n_averaged."""
+    1 / (*n_averaged + 1) (SWA), both read on the device.  Does not advance n_averaged.  ok: the non-finite guard's device flag."""
     if src.numel() < avg.numel():
         raise ValueError("source holds %d floats, the average %d" % (src.numel(), avg.numel()))
+    if ok is not None:
+        _call("mmfn_weight_average_if_f32", ptr(avg), ptr(src), avg.numel(), ptr(n_averaged), ptr(ema_weight), int(mode), ptr(ok),
+              stream())
+        return
     _call("mmfn_weight_average_f32", ptr(avg), ptr(src), avg.numel(), ptr(n_averaged), ptr(ema_weight), int(mode), stream())
 
 
-def adamw_groups_avg(p, g, m, v, step, hyper, n_groups, avg, n_averaged, ema_weight, mode, group_of=None, coef=None, n=None):
-    """adamw_groups (coef: adamw_groups_coef) that also folds every new parameter into avg[0, n) as weight_average does."""
+def adamw_groups_avg(p, g, m, v, step, hyper, n_groups, avg, n_averaged, ema_weight, mode, group_of=None, coef=None, n=None,
+                     ok=None):
+    """adamw_groups (coef: adamw_groups_coef) that also folds every new parameter into avg[0, n) as weight_average does.
+    ok (with coef): the non-finite guard's device flag."""
     n = p.numel() if n is None else n
     if avg.numel() < n:
         raise ValueError("average holds %d floats, the step covers %d" % (avg.numel(), n))
+    if ok is not None:
+        if coef is None:
+            raise ValueError("the guarded AdamW launch is the coefficient instance: pass coef")
+        _call("mmfn_adamw_groups_guard_avg_f32", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(group_of), ptr(hyper), n_groups, ptr(step),
+              ptr(coef), ptr(avg), ptr(n_averaged), ptr(ema_weight), int(mode), ptr(ok), stream())
+        return
     if coef is None:
         _call("mmfn_adamw_groups_avg_f32", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(group_of), ptr(hyper), n_groups, ptr(step), ptr(avg),
               ptr(n_averaged), ptr(ema_weight), int(mode), stream())
@@ -1202,6 +1224,47 @@ def grad_norm_finalize(partials, scale, max_norm, norm, coef=None):
     """norm = scale * sqrt(sum(partials)), coef = min(1, max_norm / (norm + 1e-6)); scale / max_norm / norm / coef: one-element
     device float tensors (views)."""
     _call("mmfn_grad_norm_finalize", ptr(partials), partials.numel(), ptr(scale), ptr(max_norm), ptr(norm), ptr(coef), stream())
+
+
+def grad_norm_finalize_guard(partials, scale, max_norm, norm, coef, ok, skipped):
+    """grad_norm_finalize that also decides the step: ok (int32 [1]) = isfinite(norm), skipped (int64 [1]) += 1 when not."""
+    _call("mmfn_grad_norm_finalize_guard", ptr(partials), partials.numel(), ptr(scale), ptr(max_norm), ptr(norm), ptr(coef), ptr(ok),
+          ptr(skipped), stream())
+
+
+def copy_if(dst, src, flag, when):
+    """dst = src (same dtype and size, contiguous) when (flag != 0) == bool(when); flag: a device int32."""
+    if dst.dtype != src.dtype or dst.numel() != src.numel() or not (dst.is_contiguous() and src.is_contiguous()):
+        raise ValueError("copy_if takes two contiguous tensors of one dtype and size")
+    _call("mmfn_copy_if", ptr(dst), ptr(src), dst.numel() * dst.element_size(), ptr(flag), 1 if when else 0, stream())
+
+
+def tensor_stats_table(ranges, device):
+    """The device table of tensor_stats for [(offset, count), ...] (float offsets into a flat buffer, multiples of 4):
+    {"table": int64 [n, 3] of (offset, count, first chunk), "n_chunks", "limit": the floats the buffer must hold}."""
+    chunk = int(lib().mmfn_tensor_stats_chunk())
+    rows, first, limit = [], 0, 0
+    for off, n in ranges:
+        if n < 1 or off % 4 or off < 0:
+            raise ValueError("tensor_stats ranges are (offset %% 4 == 0, count >= 1), got (%d, %d)" % (off, n))
+        rows.append((off, n, first))
+        first += (n + chunk - 1) // chunk
+        limit = max(limit, off + n)
+    if not rows:
+        raise ValueError("tensor_stats needs at least one range")
+    return {"table": torch.tensor(rows, dtype=torch.int64).to(device), "n_chunks": first, "limit": limit}
+
+
+def tensor_stats(flat, tab, scale=1.0):
+    """Per-tensor (|scale| * L2 norm, |scale| * max |x| over the finite entries, count of non-finite entries) of the ranges of
+    `tab` (tensor_stats_table) in the fp32 buffer `flat`: float64 [n, 3] on the device, deterministic, no host sync."""
+    if flat.dtype != torch.float32 or flat.numel() < tab["limit"]:
+        raise ValueError("the table covers %d floats, the buffer holds %d %s" % (tab["limit"], flat.numel(), flat.dtype))
+    n = tab["table"].shape[0]
+    out = torch.empty(n, 3, dtype=torch.float64, device=flat.device)
+    workspace = torch.empty(3 * tab["n_chunks"], dtype=torch.float64, device=flat.device)
+    _call("mmfn_tensor_stats_f32", ptr(flat), ptr(tab["table"]), n, tab["n_chunks"], float(scale), ptr(out), ptr(workspace), stream())
+    return out
 
 
 def ingest_rgb_u8(img_u8, out, crop=256):

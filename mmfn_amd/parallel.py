@@ -269,7 +269,12 @@ class GraphedStep(object):
     variant (gradient accumulation, Engine.accumulate_step): "step" = the plain step above; "micro" = forward, backward and
     acc += gradient per readiness group, no collective, no AdamW; "final" = the step that closes an accumulation group: the
     per-group fold (fold=True) in front of each bucket's reduction, optional clipping (clip_grad_norm), AdamW.  k, the size r of a
-    partial group, max_norm and the learning rate only change the device hyper table (set in __call__), never the capture."""
+    partial group, max_norm and the learning rate only change the device hyper table (set in __call__), never the capture.
+
+    Non-finite guard (Engine.set_nonfinite_guard): a "final" step captured while it is armed holds the guarded launches (the norm
+    is always measured, max_norm = inf without clip_grad_norm) and replays only while it stays armed; the BatchNorm snapshot of
+    a group's first micro-step is issued by __call__ in front of the replay, outside the capture.  The plain "step" variant has
+    no norm to decide on: with the guard armed use variant="final", fold=False."""
 
     def __init__(self, engine, dp, inp, gt, lr=1e-4, warm=2, single_graph=None, variant="step", clip_grad_norm=None, fold=True,
                  **adam):
@@ -279,10 +284,13 @@ class GraphedStep(object):
             raise ValueError("variant must be step / micro / final, got %r" % (variant,))
         if variant == "micro" and dp is not None:
             raise ValueError("a micro-step issues no collective: capture it without dp")
+        if variant == "step" and engine.nonfinite_guard:
+            raise ValueError('the non-finite guard is armed: capture the optimizer step as variant="final", fold=False')
         self.engine, self.dp = engine, dp
         self.variant, self.clip, self.fold = variant, clip_grad_norm, bool(fold)
         self.lr, self.adam = lr, adam
         eng = engine
+        self.guard = eng.nonfinite_guard   # the captured final_adam holds the guarded launches (or not): see __call__
         if warm and variant != "step" and eng.accum_pending:
             raise RuntimeError("warm-up steps would consume the %d pending micro-steps: capture with warm=0" % eng.accum_pending)
         for _ in range(warm):  # size every buffer / scratch lane eagerly before capture
@@ -299,9 +307,9 @@ class GraphedStep(object):
             mode = ops.ACCUM_FOLD if self.fold else ops.ACCUM_NONE
             if self.fold:
                 eng._accum_buffer()
-            if clip_grad_norm is not None:
+            if eng.guarded_clip(clip_grad_norm) is not None:
                 eng._norm_state()
-            eng.set_hyper(eng.final_rows(lr, eng.accum_pending, dp, clip_grad_norm, **adam))
+            eng.set_hyper(eng.final_rows(lr, eng.accum_pending, dp, eng.guarded_clip(clip_grad_norm), **adam))
         elif variant == "micro":
             eng._accum_buffer()
         else:
@@ -325,7 +333,7 @@ class GraphedStep(object):
                 return
             if variant == "final":
                 n_groups = len(eng._hyper_host)
-                clip = clip_grad_norm is not None
+                clip = eng.guarded_clip(clip_grad_norm) is not None
                 if dp is None or single_graph:
                     eng.backward_groups(mode, dp, clip)
                 else:
@@ -382,8 +390,12 @@ class GraphedStep(object):
             raise RuntimeError("this step was captured %s; the engine now has %s: capture the step again" % (
                 "with an attached weight average" if self.average is not None else "without a weight average",
                 "a different one" if eng.average is not None else "none"))
+        if self.variant != "micro" and eng.nonfinite_guard != self.guard:
+            raise RuntimeError("this step was captured with the non-finite guard %s; the engine now has it %s: capture the step again"
+                               % (("armed", "disarmed") if self.guard else ("disarmed", "armed")))
         if self.variant == "final":
-            eng.set_hyper(eng.final_rows(self.lr, pending, self.dp, self.clip, **self.adam))
+            eng.set_hyper(eng.final_rows(self.lr, pending, self.dp, eng.guarded_clip(self.clip), **self.adam))
+        eng.guard_snapshot()   # (guard armed, first micro-step of a group: the BatchNorm state a skipped step returns to)
         if self.dp is not None and not self.single_graph:
             self.dp.begin()   # (single graph: the bucket bookkeeping only ran at capture time)
         self.recorder.replay()

@@ -57,10 +57,13 @@ class Trainer(object):
         # that have an average
         self.val_loss_average = []
         self.bestval_average = 1e10
+        # optimizer steps the non-finite guard skipped (train(skip_nonfinite=True)); None = the option was never on, and recent.log
+        # then has no such key
+        self.skipped_steps = None
 
     # ------------------------------------------------------------------ one epoch of training
     def train(self, model, dataloader_train, config, optimizer, dp=None, fused=True, log_every=50, on_log=None, graph=True,
-              lane_bucket=16, accum_steps=1, clip_grad_norm=None, average=None):
+              lane_bucket=16, accum_steps=1, clip_grad_norm=None, average=None, skip_nonfinite=False):
         """One epoch.  graph=True (fused path): the second batch of a given shape captures the step into hipGraphs over
         static input buffers and every later batch of that shape only copies its inputs and replays (the first one runs
         eagerly and sizes the buffers); lane sets are zero-padded to a multiple of `lane_bucket` lanes so that ragged
@@ -78,25 +81,39 @@ class Trainer(object):
 
         average (averaging.AveragedMMFN): updated after every optimizer step of the epoch - attached to the engine for the
         epoch, inside the fused step's AdamW launch (eager and replayed, captured as shapes of their own; micro-steps do not
-        update it); fused=False: its update_parameters() after each optimizer.step()."""
-        if average is None or not fused:
+        update it); fused=False: its update_parameters() after each optimizer.step().
+
+        skip_nonfinite: the engine's non-finite guard (Engine.set_nonfinite_guard) is armed for the epoch: an optimizer step
+        whose gradient norm is not finite is skipped on the device - weights, moments, BatchNorm statistics and the average stay
+        as they were, the whole accumulation group is dropped.  on_log and recent.log gain "skipped_steps" (the run's count), the
+        epoch's train_loss is the mean over the batches with a finite loss, and a log window (log_every batches, or the rest of
+        the epoch) in which EVERY optimizer step was skipped raises RuntimeError naming tensors with non-finite gradients."""
+        if skip_nonfinite and not fused:
+            raise NotImplementedError("skip_nonfinite is an option of the fused step (fused=True)")
+        if (average is None and not skip_nonfinite) or not fused:
             return self._train(model, dataloader_train, config, optimizer, dp, fused, log_every, on_log, graph, lane_bucket,
                                accum_steps, clip_grad_norm, average)
         eng = model._engine_for()
-        eng.attach_average(average)
+        if average is not None:
+            eng.attach_average(average)
         try:
+            if skip_nonfinite:
+                eng.set_nonfinite_guard(True)
             return self._train(model, dataloader_train, config, optimizer, dp, fused, log_every, on_log, graph, lane_bucket,
-                               accum_steps, clip_grad_norm, average)
+                               accum_steps, clip_grad_norm, average, skip_nonfinite)
         finally:
-            eng.detach_average()
+            if skip_nonfinite:
+                eng.set_nonfinite_guard(False)
+            if average is not None:
+                eng.detach_average()
 
     def _train(self, model, dataloader_train, config, optimizer, dp, fused, log_every, on_log, graph, lane_bucket, accum_steps,
-               clip_grad_norm, average):
-        """Trainer.train's epoch loop (an attached average is the caller's)."""
+               clip_grad_norm, average, guard=False):
+        """Trainer.train's epoch loop (an attached average and the armed guard are the caller's)."""
         accum_steps = int(accum_steps)
         if accum_steps < 1:
             raise ValueError("accum_steps must be >= 1, got %d" % accum_steps)
-        accumulating = accum_steps > 1 or clip_grad_norm is not None
+        accumulating = accum_steps > 1 or clip_grad_norm is not None or guard
         if accumulating and not fused:
             raise NotImplementedError("accum_steps / clip_grad_norm are options of the fused step (fused=True)")
         model.train()
@@ -109,6 +126,13 @@ class Trainer(object):
         total = torch.zeros(1, dtype=torch.float32, device=model._layout.device)
         window = torch.zeros_like(total)
         num_batches = 0
+        if guard:
+            # losses are summed over the batches where they are finite, counted on the device: [epoch, window]
+            finite = torch.zeros(2, dtype=torch.float32, device=model._layout.device)
+            if self.skipped_steps is None:
+                self.skipped_steps = 0
+            skipped_base = self.skipped_steps - int(eng.skipped_steps.item())   # the run's count = base + the engine's
+            window_steps, window_skipped0 = 0, self.skipped_steps
         batches = D.DevicePrefetcher(dataloader_train, self.device, config, variant=model.variant)
         # (accumulating: one batch of look-ahead tells the epoch's last batch, which closes the partial group)
         for (args, gt), last in (_with_last(batches) if accumulating else ((b, False) for b in batches)):
@@ -122,6 +146,8 @@ class Trainer(object):
                 loss = self._accum_call(eng, dp, inp, gt, lr, adam, final, accum_steps > 1, clip_grad_norm, graph, average)
                 if final:
                     in_group = 0
+                    if guard:
+                        window_steps += 1
             elif fused:
                 inp = args if isinstance(args, dict) else model._pack(*args)  # raw-frame batches are engine inputs already
                 # per-group (lr, beta1, beta2, eps, weight_decay): read every step, so an LR scheduler just works - they go
@@ -164,19 +190,49 @@ class Trainer(object):
                 if average is not None:
                     average.update_parameters(model)
                 loss = loss.detach().view(1)
+            if guard:
+                good = torch.isfinite(loss)
+                loss = torch.where(good, loss, torch.zeros_like(loss))
+                finite += good.to(finite.dtype)
             total += loss
             window += loss
             self.cur_iter += 1
             num_batches += 1
+            if guard and num_batches % log_every == 0:
+                # one read per window: the skip count, and with it the check that the window made progress
+                self.skipped_steps = skipped_base + int(eng.skipped_steps.item())
+                self._check_progress(eng, window_steps, self.skipped_steps - window_skipped0)
+                window_steps, window_skipped0 = 0, self.skipped_steps
             if on_log is not None and num_batches % log_every == 0:
-                rec = {"loss": float(window.item()) / log_every, "iter": self.cur_iter}
+                if guard:   # (the window's mean over its finite losses)
+                    rec = {"loss": float(window.item()) / max(float(finite[1].item()), 1.0), "iter": self.cur_iter,
+                           "skipped_steps": self.skipped_steps}
+                    finite[1] = 0
+                else:
+                    rec = {"loss": float(window.item()) / log_every, "iter": self.cur_iter}
                 if clip_grad_norm is not None:   # (None until the first optimizer step of the run)
                     rec["grad_norm"] = None if eng.last_grad_norm is None else float(eng.last_grad_norm.item())
                 on_log(rec)
                 window.zero_()
-        self.train_loss.append(float(total.item()) / max(num_batches, 1))
+        if guard:
+            self.skipped_steps = skipped_base + int(eng.skipped_steps.item())
+            self._check_progress(eng, window_steps, self.skipped_steps - window_skipped0)
+            self.train_loss.append(float(total.item()) / max(float(finite[0].item()), 1.0))
+        else:
+            self.train_loss.append(float(total.item()) / max(num_batches, 1))
         self.cur_epoch += 1
         return self.train_loss[-1]
+
+    @staticmethod
+    def _check_progress(eng, steps, skipped):
+        """skip_nonfinite: a window whose optimizer steps were ALL skipped is a run that has stopped training - say which tensors'
+        gradients are not finite (Engine.tensor_stats, the last step's gradient) instead of spinning."""
+        if steps == 0 or skipped < steps:
+            return
+        names, table = eng.tensor_stats("grads")
+        bad = [n for n, c in zip(names, table[:, 2].tolist()) if c > 0]
+        raise RuntimeError("all %d optimizer step(s) since the last check were skipped: the gradient is not finite in %d of %d tensors "
+                           "(%s%s)" % (steps, len(bad), len(names), ", ".join(bad[:5]), ", ..." if len(bad) > 5 else ""))
 
     def _accum_call(self, eng, dp, inp, gt, lr, adam, final, fold, clip, graph, average=None):
         """One batch of an accumulation group: a micro-step, or (final) the step that closes the group.  graph=True: per
@@ -187,6 +243,8 @@ class Trainer(object):
         sig = (StaticBatchStep.signature(inp, gt), variant, fold, clip is not None)
         if average is not None and final:
             sig = sig + ("average",)
+        if eng.nonfinite_guard and final:   # (the guarded launches are a capture of their own; micro-steps have none)
+            sig = sig + ("guard",)
         state = self._static_steps.pop(sig, None)
         if state is not None and state != "eager":
             if state == "seen":
@@ -310,6 +368,8 @@ class Trainer(object):
             table["average"] = {"mode": average.mode, "decay": average.decay, "use_buffers": average.use_buffers,
                                 "n_averaged": int(average.n_averaged.item())}
             table["val_loss_average"], table["bestval_average"] = self.val_loss_average, self.bestval_average
+        if self.skipped_steps is not None:
+            table["skipped_steps"] = self.skipped_steps
         table["files"] = {n: _stamp(os.path.join(logdir, n)) for n in files if os.path.isfile(os.path.join(logdir, n))}
         with open(tmp, "w") as f:
             f.write(json.dumps(table))
@@ -334,6 +394,8 @@ class Trainer(object):
         self.bestval_epoch = table.get("bestval_epoch", self.cur_epoch)
         self.train_loss = table["train_loss"]
         self.val_loss = table["val_loss"]
+        if "skipped_steps" in table:
+            self.skipped_steps = table["skipped_steps"]
         names = ("best_model.pth", "best_optim.pth") if which == "best" else ("model.pth", "recent_optim.pth")
         if not all(os.path.isfile(os.path.join(logdir, n)) for n in names):
             # no validation set / no improvement yet: save() never wrote the best_* pair - continue from the recent one
@@ -441,7 +503,8 @@ def _plain_state_dict(model):
 
 
 def fit(model, optimizer, train_loader, val_loader, config, logdir, epochs, val_every=1, save_every=1, dp=None, rank=0,
-        on_log=None, dist=None, accum_steps=1, clip_grad_norm=None, average=None, average_every="step", average_start_epoch=0):
+        on_log=None, dist=None, accum_steps=1, clip_grad_norm=None, average=None, average_every="step", average_start_epoch=0,
+        skip_nonfinite=False):
     """The epoch loop of phase2_train_net.py:307-322: train every epoch; rank 0 validates every `val_every`
     epochs and saves every `save_every`.  Data parallel: pass `dp` (a parallel.DataParallel), or just the initialised
     torch.distributed module as `dist` - the transport is then chosen by parallel.connect: the C-ABI RCCL communicator when it
@@ -452,7 +515,9 @@ def fit(model, optimizer, train_loader, val_loader, config, logdir, epochs, val_
     average (averaging.AveragedMMFN): average_every="step" updates it in every optimizer step (inside the AdamW launch) from epoch
     average_start_epoch on; "epoch" calls its update_parameters() at the end of each such epoch (the SWA schedule).  Rank 0 also
     validates average.module into trainer.val_loss_average and saves averaged_model.pth / best_averaged_model.pth; every rank
-    keeps its own copy, in lock step because the parameters are (DataParallel.broadcast_average after a resume)."""
+    keeps its own copy, in lock step because the parameters are (DataParallel.broadcast_average after a resume).
+    skip_nonfinite: Trainer.train's option, every epoch (a skipped step is skipped on every rank: the norm is taken after the
+    gradient reduction)."""
     if average_every not in ("step", "epoch"):
         raise ValueError("average_every must be 'step' or 'epoch', got %r" % (average_every,))
     if dp is None and dist is not None and dist.get_world_size() > 1:
@@ -473,7 +538,8 @@ def fit(model, optimizer, train_loader, val_loader, config, logdir, epochs, val_
             sampler.set_epoch(epoch)
         averaging = average is not None and epoch >= average_start_epoch
         trainer.train(model, train_loader, config, optimizer, dp=dp, on_log=on_log if rank == 0 else None, accum_steps=accum_steps,
-                      clip_grad_norm=clip_grad_norm, average=average if averaging and average_every == "step" else None)
+                      clip_grad_norm=clip_grad_norm, average=average if averaging and average_every == "step" else None,
+                      skip_nonfinite=skip_nonfinite)
         if averaging and average_every == "epoch":
             average.update_parameters(model)
         if epoch % val_every == 0 and rank == 0 and val_loader is not None:
