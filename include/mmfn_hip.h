@@ -512,16 +512,6 @@ int mmfn_gru_head_bwd_f32(const float* pred, const float* gt, const float* dpred
 int mmfn_step_advance(int64_t* step, void* stream);
 int mmfn_adamw_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                    float weight_decay, const int64_t* step, float grad_scale, void* stream);
-/* torch.optim.AdamW with param_groups (the reference's decay / no-decay split, model_vec.py:179-209) and hyper-parameters
- * in DEVICE memory, so a learning-rate schedule does not invalidate a captured hipGraph.  hyper: [n_groups][8] floats
- * {lr, beta1, beta2, eps, weight_decay, grad_scale, 0, 0}; group_of: one group id per 4 consecutive parameters (tensors
- * of the flat layout are 16-byte aligned), NULL = all group 0; n must be a multiple of 4; n_groups <= 16. */
-int mmfn_adamw_groups_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of, const float* hyper,
-                          int n_groups, const int64_t* step, void* stream);
-/* the same step with every group's grad_scale multiplied by *coef (device memory: the clip coefficient of
- * mmfn_grad_norm_finalize, so clipping needs no host round trip and stays inside a captured hipGraph) */
-int mmfn_adamw_groups_coef_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of,
-                               const float* hyper, int n_groups, const int64_t* step, const float* coef, void* stream);
 
 /* ---- weight averaging (torch.optim.swa_utils.AveragedModel: EMA / SWA) ---------------------------------------------- */
 #define MMFN_AVG_EMA 0 /* w = *ema_w: fp32(1 - decay), formed on the host as torch forms it */
@@ -532,14 +522,25 @@ int mmfn_adamw_groups_coef_f32(float* p, const float* g, float* m, float* v, int
  * after the update).  Else MMFN_EINVAL. */
 int mmfn_weight_average_f32(float* avg, const float* src, int64_t n, const int64_t* n_averaged, const float* ema_w, int mode,
                             void* stream);
-/* mmfn_adamw_groups_f32 / mmfn_adamw_groups_coef_f32 that also fold each NEW parameter into avg[0, n) as mmfn_weight_average_f32
- * does (one pass: +8 B per parameter) */
-int mmfn_adamw_groups_avg_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of, const float* hyper,
-                              int n_groups, const int64_t* step, float* avg, const int64_t* n_averaged, const float* ema_w, int mode,
-                              void* stream);
-int mmfn_adamw_groups_coef_avg_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of,
-                                   const float* hyper, int n_groups, const int64_t* step, const float* coef, float* avg,
-                                   const int64_t* n_averaged, const float* ema_w, int mode, void* stream);
+/* torch.optim.AdamW with param_groups (the reference's decay / no-decay split, model_vec.py:179-209) and hyper-parameters
+ * in DEVICE memory, so a learning-rate schedule does not invalidate a captured hipGraph.  hyper: [n_groups][8] floats
+ * {lr, beta1, beta2, eps, weight_decay, grad_scale, 0, 0}; group_of: one group id per 4 consecutive parameters (tensors
+ * of the flat layout are 16-byte aligned), NULL = all group 0; n must be a multiple of 4; n_groups <= 16.
+ * The bits of `variant` select the kernel instance; a set bit makes its pointers mandatory (else
+ * MMFN_EINVAL), the pointers of a clear bit are ignored.  Valid: 0, COEF, AVG, COEF|AVG, COEF|GUARD, COEF|AVG|GUARD; anything else
+ * is MMFN_EINVAL.
+ *   COEF   every group's grad_scale is multiplied by *coef (device memory: the clip coefficient of mmfn_grad_norm_finalize, so
+ *          clipping needs no host round trip and stays inside a captured hipGraph)
+ *   AVG    each NEW parameter is also folded into avg[0, n) as mmfn_weight_average_f32 does (one pass: +8 B per parameter);
+ *          avg, n_averaged, ema_w, avg_mode as there
+ *   GUARD  the whole launch sits behind *ok (int32 in device memory, 4-byte aligned: the non-finite guard's flag of
+ *          mmfn_grad_norm_finalize_guard): bit-identical to the unguarded instance when *ok, no access at all otherwise */
+#define MMFN_ADAMW_COEF 1
+#define MMFN_ADAMW_AVG 2
+#define MMFN_ADAMW_GUARD 4
+int mmfn_adamw_groups_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of, const float* hyper,
+                          int n_groups, const int64_t* step, int variant, const float* coef, float* avg, const int64_t* n_averaged,
+                          const float* ema_w, int avg_mode, const int32_t* ok, void* stream);
 
 /* ---- gradient accumulation and global-norm clipping over the flat gradient buffer ------------------------------ */
 #define MMFN_ACCUM_NONE 0 /* read g only (needs partials) */
@@ -557,17 +558,12 @@ int mmfn_grad_norm_finalize(const double* partials, int n_partials, const float*
 
 /* ---- non-finite guard: the optimizer step decided on the device, inside a captured hipGraph --------------------- */
 /* mmfn_grad_norm_finalize plus the decision: *ok = isfinite(*norm) (int32, 1 = take the step), *skipped += 1 when not (int64).
- * coef and max_norm are required here.  The launches below read *ok and do nothing at all when it is 0. */
+ * coef and max_norm are required here.  The launches below and the GUARD instances of mmfn_adamw_groups_f32 read *ok
+ * and do nothing at all when it is 0. */
 int mmfn_grad_norm_finalize_guard(const double* partials, int n_partials, const float* scale, const float* max_norm, float* norm,
                                   float* coef, int32_t* ok, int64_t* skipped, void* stream);
 /* *step += 1 when *ok */
 int mmfn_step_advance_if(int64_t* step, const int32_t* ok, void* stream);
-/* mmfn_adamw_groups_coef_f32 / mmfn_adamw_groups_coef_avg_f32 behind *ok: bit-identical to them when *ok, no access otherwise */
-int mmfn_adamw_groups_guard_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of, const float* hyper,
-                                int n_groups, const int64_t* step, const float* coef, const int32_t* ok, void* stream);
-int mmfn_adamw_groups_guard_avg_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of,
-                                    const float* hyper, int n_groups, const int64_t* step, const float* coef, float* avg,
-                                    const int64_t* n_averaged, const float* ema_w, int mode, const int32_t* ok, void* stream);
 /* mmfn_weight_average_f32 behind *ok */
 int mmfn_weight_average_if_f32(float* avg, const float* src, int64_t n, const int64_t* n_averaged, const float* ema_w, int mode,
                                const int32_t* ok, void* stream);

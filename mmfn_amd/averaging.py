@@ -6,7 +6,7 @@ AveragedModel deep-copies the module and lerps its standalone parameter tensors;
 variant and config, so `.module` is validated, checkpointed and deployed like the live model.  Updates:
   * update_parameters(model): torch's API, one launch over the flat buffer (mmfn_weight_average_f32) + the BatchNorm buffers;
   * Engine.attach_average(avg): every optimizer step of the fused path folds the new weights into the average inside the
-    AdamW launch (mmfn_adamw_groups_avg_f32), eager or graph-replayed.
+    AdamW launch (mmfn_adamw_groups_f32 with MMFN_ADAMW_AVG), eager or graph-replayed.
 The weight is formed as torch forms it (EMA: fp32(1 - decay) from a Python float; SWA: 1 / (n_averaged + 1) in fp32 on the
 device), the first update copies, and both n_averaged and the EMA weight live in device memory (a captured step stays valid).
 """

@@ -196,54 +196,32 @@ bool avg_args_ok(const AvgArgs& a) {
   if (!a.avg || ((uintptr_t)a.avg & 15) || !a.n_averaged || ((uintptr_t)a.n_averaged & 7)) return false;
   return a.mode != MMFN_AVG_EMA || (a.ema_w && !((uintptr_t)a.ema_w & 3));
 }
+bool flag_ok(const int32_t* ok) { return ok && !((uintptr_t)ok & 3); }   // the non-finite guard's device flag
+}  // namespace
+
+// One entry point for the six instances of adamw_groups_kernel: the bits of `variant` (MMFN_ADAMW_COEF | _AVG | _GUARD) are the
+// template arguments.  A set bit makes its pointers mandatory; the pointers of a clear bit are ignored.
+namespace {
+using AdamwGroupsKernel = decltype(&adamw_groups_kernel<false, false, false>);
+const AdamwGroupsKernel kAdamwGroups[8] = {   // by variant; nullptr: GUARD without COEF, which is not built
+    adamw_groups_kernel<false, false, false>, adamw_groups_kernel<true, false, false>, adamw_groups_kernel<false, true, false>,
+    adamw_groups_kernel<true, true, false>,   nullptr, adamw_groups_kernel<true, false, true>, nullptr,
+    adamw_groups_kernel<true, true, true>};
 }  // namespace
 
 extern "C" int mmfn_adamw_groups_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of,
-                                     const float* hyper, int n_groups, const int64_t* step, void* stream) {
+                                     const float* hyper, int n_groups, const int64_t* step, int variant, const float* coef,
+                                     float* avg, const int64_t* n_averaged, const float* ema_w, int avg_mode, const int32_t* ok,
+                                     void* stream) {
   if (n <= 0) return 0;
-  if (!step || !hyper || n_groups < 1 || n_groups > MMFN_ADAMW_MAX_GROUPS || (n & 3) ||
-      (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15))
+  if (variant < 0 || variant >= 8 || !kAdamwGroups[variant]) return MMFN_EINVAL;
+  const bool with_coef = variant & MMFN_ADAMW_COEF, with_avg = variant & MMFN_ADAMW_AVG, guard = variant & MMFN_ADAMW_GUARD;
+  const AvgArgs a = with_avg ? AvgArgs{avg, n_averaged, ema_w, avg_mode} : AvgArgs{};
+  if (!adamw_args_ok(p, g, m, v, n, hyper, n_groups, step) || (with_coef && !coef) || (with_avg && !avg_args_ok(a)) ||
+      (guard && !flag_ok(ok)))
     return MMFN_EINVAL;
-  const int blocks = (int)std::min<int64_t>(ceil_div64(n / 4, 256), 4096);
-  hipLaunchKernelGGL((adamw_groups_kernel<false, false, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, group_of,
-                     hyper, n_groups, step, (const float*)nullptr, AvgArgs{}, (const int32_t*)nullptr);
-  MMFN_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int mmfn_adamw_groups_coef_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of,
-                                          const float* hyper, int n_groups, const int64_t* step, const float* coef, void* stream) {
-  if (n <= 0) return 0;
-  if (!step || !hyper || !coef || n_groups < 1 || n_groups > MMFN_ADAMW_MAX_GROUPS || (n & 3) ||
-      (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15))
-    return MMFN_EINVAL;
-  const int blocks = (int)std::min<int64_t>(ceil_div64(n / 4, 256), 4096);
-  hipLaunchKernelGGL((adamw_groups_kernel<true, false, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, group_of,
-                     hyper, n_groups, step, coef, AvgArgs{}, (const int32_t*)nullptr);
-  MMFN_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int mmfn_adamw_groups_avg_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of,
-                                         const float* hyper, int n_groups, const int64_t* step, float* avg, const int64_t* n_averaged,
-                                         const float* ema_w, int mode, void* stream) {
-  if (n <= 0) return 0;
-  const AvgArgs a{avg, n_averaged, ema_w, mode};
-  if (!adamw_args_ok(p, g, m, v, n, hyper, n_groups, step) || !avg_args_ok(a)) return MMFN_EINVAL;
-  hipLaunchKernelGGL((adamw_groups_kernel<false, true, false>), dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
-                     group_of, hyper, n_groups, step, (const float*)nullptr, a, (const int32_t*)nullptr);
-  MMFN_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int mmfn_adamw_groups_coef_avg_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of,
-                                              const float* hyper, int n_groups, const int64_t* step, const float* coef, float* avg,
-                                              const int64_t* n_averaged, const float* ema_w, int mode, void* stream) {
-  if (n <= 0) return 0;
-  const AvgArgs a{avg, n_averaged, ema_w, mode};
-  if (!coef || !adamw_args_ok(p, g, m, v, n, hyper, n_groups, step) || !avg_args_ok(a)) return MMFN_EINVAL;
-  hipLaunchKernelGGL((adamw_groups_kernel<true, true, false>), dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
-                     group_of, hyper, n_groups, step, coef, a, (const int32_t*)nullptr);
+  hipLaunchKernelGGL(kAdamwGroups[variant], dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, group_of, hyper,
+                     n_groups, step, with_coef ? coef : nullptr, a, guard ? ok : nullptr);
   MMFN_LAUNCH_CHECK();
   return 0;
 }
@@ -260,34 +238,6 @@ extern "C" int mmfn_weight_average_f32(float* avg, const float* src, int64_t n, 
 }
 
 // ---- the non-finite guard's forms: the same launches behind the device flag *ok (1 = take the step, 0 = skip it) -------------
-namespace {
-bool flag_ok(const int32_t* ok) { return ok && !((uintptr_t)ok & 3); }
-}  // namespace
-
-extern "C" int mmfn_adamw_groups_guard_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of,
-                                           const float* hyper, int n_groups, const int64_t* step, const float* coef, const int32_t* ok,
-                                           void* stream) {
-  if (n <= 0) return 0;
-  if (!coef || !flag_ok(ok) || !adamw_args_ok(p, g, m, v, n, hyper, n_groups, step)) return MMFN_EINVAL;
-  hipLaunchKernelGGL((adamw_groups_kernel<true, false, true>), dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
-                     group_of, hyper, n_groups, step, coef, AvgArgs{}, ok);
-  MMFN_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int mmfn_adamw_groups_guard_avg_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of,
-                                               const float* hyper, int n_groups, const int64_t* step, const float* coef, float* avg,
-                                               const int64_t* n_averaged, const float* ema_w, int mode, const int32_t* ok,
-                                               void* stream) {
-  if (n <= 0) return 0;
-  const AvgArgs a{avg, n_averaged, ema_w, mode};
-  if (!coef || !flag_ok(ok) || !adamw_args_ok(p, g, m, v, n, hyper, n_groups, step) || !avg_args_ok(a)) return MMFN_EINVAL;
-  hipLaunchKernelGGL((adamw_groups_kernel<true, true, true>), dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
-                     group_of, hyper, n_groups, step, coef, a, ok);
-  MMFN_LAUNCH_CHECK();
-  return 0;
-}
-
 extern "C" int mmfn_weight_average_if_f32(float* avg, const float* src, int64_t n, const int64_t* n_averaged, const float* ema_w,
                                           int mode, const int32_t* ok, void* stream) {
   if (n <= 0) return 0;

@@ -1811,7 +1811,6 @@ class Engine(object):
     def optimizer_step(self, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0, groups=None):
         """torch.optim.AdamW step over the trained range of the flat buffer.  `groups`: per-group
         (lr, beta1, beta2, eps, weight_decay) rows (FusedAdamW.hyper_rows()); default one group from the scalars."""
-        L = self.layout
         if self.accum_pending:
             raise RuntimeError("%d accumulated micro-step(s) are pending: finish them with train_step() or drop them with "
                                "discard_accumulated() before a direct optimizer_step()" % self.accum_pending)
@@ -1819,12 +1818,7 @@ class Engine(object):
         self.set_hyper(groups)
         self.module.weights_changed()
         ops.step_advance(self.step_count)
-        group_of = self.opt_group_of if len(groups) > 1 else None
-        if self.average is not None:
-            self._adamw_average(len(groups), group_of)
-            return
-        ops.adamw_groups(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self.step_count, self.opt_hyper, len(groups),
-                         group_of=group_of, n=L.tail)
+        self._adamw(len(groups))
 
     # ------------------------------------------------------------------ weight average (mmfn_amd.averaging)
     def attach_average(self, avg):
@@ -1840,20 +1834,18 @@ class Engine(object):
     def detach_average(self):
         self.average = None
 
-    def _adamw_average(self, n_groups, group_of, coef=None, ok=None):
-        """The AdamW launch with the attached average folded in (coef: the clipping instance), then the average's BatchNorm
-        buffers and its count: three launches (+ a counter copy) instead of one.  ok: the non-finite guard's flag, every one of
-        them behind it."""
+    def _adamw(self, n_groups, coef=None, ok=None):
+        """The AdamW launch over the trained range (coef: the clipping instance).  With an attached average it is folded into the
+        launch, then come the average's BatchNorm buffers and its count: three launches (+ a counter copy) instead of one.  ok:
+        the non-finite guard's flag, every one of them behind it."""
         L, a = self.layout, self.average
-        ops.adamw_groups_avg(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self.step_count, self.opt_hyper, n_groups,
-                             a.module._layout.params, a.n_averaged, a.ema_weight, a.mode_code, group_of=group_of, coef=coef, n=L.tail,
-                             ok=ok)
-        a.update_buffers(self.module, ok=ok)
-        if ok is None:
-            ops.step_advance(a.n_averaged)
-        else:
-            ops.step_advance_if(a.n_averaged, ok)
-        a.module.weights_changed()
+        avg = None if a is None else (a.module._layout.params, a.n_averaged, a.ema_weight, a.mode_code)
+        ops.adamw_groups(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self.step_count, self.opt_hyper, n_groups,
+                         group_of=self.opt_group_of if n_groups > 1 else None, n=L.tail, coef=coef, avg=avg, ok=ok)
+        if a is not None:
+            a.update_buffers(self.module, ok=ok)
+            ops.step_advance(a.n_averaged, ok=ok)
+            a.module.weights_changed()
 
     # ------------------------------------------------------------------ non-finite guard
     def set_nonfinite_guard(self, on=True):
@@ -2077,7 +2069,7 @@ class Engine(object):
         self.module.weights_changed()
         if guard is None:
             ops.step_advance(self.step_count)
-        group_of = self.opt_group_of if n_groups > 1 else None
+        coef = ok = None
         if clip:
             nm = self._norm_state()
             if dp is not None:
@@ -2087,24 +2079,12 @@ class Engine(object):
             else:
                 part = nm["partials"][:nm["n_group_slots"]]
             out = nm["out"]
-            ok = None
-            if guard is None:
-                ops.grad_norm_finalize(part, self.opt_hyper[0, 5:6], self.opt_hyper[0, 6:7], out[0:1], out[1:2])
-            else:
-                ok = guard["ok"]
-                ops.grad_norm_finalize_guard(part, self.opt_hyper[0, 5:6], self.opt_hyper[0, 6:7], out[0:1], out[1:2], ok,
-                                             guard["skipped"])
-                ops.step_advance_if(self.step_count, ok)
+            coef = out[1:2]
+            ok, skipped = (None, None) if guard is None else (guard["ok"], guard["skipped"])
+            ops.grad_norm_finalize(part, self.opt_hyper[0, 5:6], self.opt_hyper[0, 6:7], out[0:1], coef, ok=ok, skipped=skipped)
+            if guard is not None:
+                ops.step_advance(self.step_count, ok=ok)
                 ops.copy_if(L.buffers_flat, guard["buffers"], ok, when=False)    # skipped: the group's BatchNorm updates go
                 ops.copy_if(L.counters_flat, guard["counters"], ok, when=False)
-            if self.average is not None:
-                self._adamw_average(n_groups, group_of, coef=out[1:2], ok=ok)
-            else:
-                ops.adamw_groups_coef(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self.step_count, self.opt_hyper, n_groups, out[1:2],
-                                      group_of=group_of, n=L.tail, ok=ok)
-        elif self.average is not None:
-            self._adamw_average(n_groups, group_of)
-        else:
-            ops.adamw_groups(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self.step_count, self.opt_hyper, n_groups,
-                             group_of=group_of, n=L.tail)
+        self._adamw(n_groups, coef=coef, ok=ok)
         self.accum_pending = 0

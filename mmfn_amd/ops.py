@@ -1131,13 +1131,12 @@ def gru_head_bwd(pred, gt, dpred, gscale, w_ih, w_hh, w_out, hs, gates, xin, dz0
           ptr(gates), ptr(xin), ptr(dz0), ptr(part), B, steps, stream())
 
 
-def step_advance(step):
+def step_advance(step, ok=None):
+    """step += 1; ok: the non-finite guard's device flag (int32), only when it is set."""
+    if ok is not None:
+        _call("mmfn_step_advance_if", ptr(step), ptr(ok), stream())
+        return
     _call("mmfn_step_advance", ptr(step), stream())
-
-
-def step_advance_if(step, ok):
-    """step += 1 when the device flag `ok` (int32) is set."""
-    _call("mmfn_step_advance_if", ptr(step), ptr(ok), stream())
 
 
 def rng_advance(state):
@@ -1148,24 +1147,6 @@ def adamw(p, g, m, v, step, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8, weight_de
     n = p.numel() if n is None else n
     _call("mmfn_adamw_f32", ptr(p), ptr(g), ptr(m), ptr(v), n, lr, beta1, beta2, eps, weight_decay, ptr(step),
           float(grad_scale), stream())
-
-
-def adamw_groups(p, g, m, v, step, hyper, n_groups, group_of=None, n=None):
-    """AdamW with the hyper-parameter rows (and optional per-float4 group ids) in device memory."""
-    n = p.numel() if n is None else n
-    _call("mmfn_adamw_groups_f32", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(group_of), ptr(hyper), n_groups, ptr(step), stream())
-
-
-def adamw_groups_coef(p, g, m, v, step, hyper, n_groups, coef, group_of=None, n=None, ok=None):
-    """adamw_groups with every group's grad_scale multiplied by the device scalar `coef` (the clip coefficient).  ok: the
-    non-finite guard's device flag (int32): the launch touches nothing when it is 0."""
-    n = p.numel() if n is None else n
-    if ok is not None:
-        _call("mmfn_adamw_groups_guard_f32", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(group_of), ptr(hyper), n_groups, ptr(step),
-              ptr(coef), ptr(ok), stream())
-        return
-    _call("mmfn_adamw_groups_coef_f32", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(group_of), ptr(hyper), n_groups, ptr(step), ptr(coef),
-          stream())
 
 
 AVG_EMA, AVG_SWA = 0, 1   # mirror include/mmfn_hip.h
@@ -1183,25 +1164,23 @@ def weight_average(avg, src, n_averaged, ema_weight, mode, ok=None):
     _call("mmfn_weight_average_f32", ptr(avg), ptr(src), avg.numel(), ptr(n_averaged), ptr(ema_weight), int(mode), stream())
 
 
-def adamw_groups_avg(p, g, m, v, step, hyper, n_groups, avg, n_averaged, ema_weight, mode, group_of=None, coef=None, n=None,
-                     ok=None):
-    """adamw_groups (coef: adamw_groups_coef) that also folds every new parameter into avg[0, n) as weight_average does.
-    ok (with coef): the non-finite guard's device flag."""
+ADAMW_COEF, ADAMW_AVG, ADAMW_GUARD = 1, 2, 4   # mirror include/mmfn_hip.h
+
+
+def adamw_groups(p, g, m, v, step, hyper, n_groups, group_of=None, n=None, coef=None, avg=None, ok=None):
+    """AdamW with the hyper-parameter rows (and optional per-float4 group ids) in device memory.  coef: a device scalar that
+    multiplies every group's grad_scale (the clip coefficient).  avg: (avg, n_averaged, ema_weight, mode), every new parameter is
+    also folded into avg[0, n) as weight_average does.  ok (with coef): the non-finite guard's device flag (int32), the launch
+    touches nothing when it is 0."""
     n = p.numel() if n is None else n
-    if avg.numel() < n:
-        raise ValueError("average holds %d floats, the step covers %d" % (avg.numel(), n))
-    if ok is not None:
-        if coef is None:
-            raise ValueError("the guarded AdamW launch is the coefficient instance: pass coef")
-        _call("mmfn_adamw_groups_guard_avg_f32", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(group_of), ptr(hyper), n_groups, ptr(step),
-              ptr(coef), ptr(avg), ptr(n_averaged), ptr(ema_weight), int(mode), ptr(ok), stream())
-        return
-    if coef is None:
-        _call("mmfn_adamw_groups_avg_f32", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(group_of), ptr(hyper), n_groups, ptr(step), ptr(avg),
-              ptr(n_averaged), ptr(ema_weight), int(mode), stream())
-    else:
-        _call("mmfn_adamw_groups_coef_avg_f32", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(group_of), ptr(hyper), n_groups, ptr(step),
-              ptr(coef), ptr(avg), ptr(n_averaged), ptr(ema_weight), int(mode), stream())
+    a, n_averaged, ema_weight, mode = (None, None, None, 0) if avg is None else avg
+    if a is not None and a.numel() < n:
+        raise ValueError("average holds %d floats, the step covers %d" % (a.numel(), n))
+    if ok is not None and coef is None:
+        raise ValueError("the guarded AdamW launch is the coefficient instance: pass coef")
+    variant = sum(bit for bit, arg in ((ADAMW_COEF, coef), (ADAMW_AVG, avg), (ADAMW_GUARD, ok)) if arg is not None)
+    _call("mmfn_adamw_groups_f32", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(group_of), ptr(hyper), n_groups, ptr(step), variant,
+          ptr(coef), ptr(a), ptr(n_averaged), ptr(ema_weight), int(mode), ptr(ok), stream())
 
 
 ACCUM_NONE, ACCUM_ADD, ACCUM_FOLD = 0, 1, 2   # mirror include/mmfn_hip.h
@@ -1220,16 +1199,15 @@ def grad_accum(g, acc, mode, partials=None):
     _call("mmfn_grad_accum_f32", ptr(g), ptr(acc), g.numel(), int(mode), ptr(partials), stream())
 
 
-def grad_norm_finalize(partials, scale, max_norm, norm, coef=None):
+def grad_norm_finalize(partials, scale, max_norm, norm, coef=None, ok=None, skipped=None):
     """norm = scale * sqrt(sum(partials)), coef = min(1, max_norm / (norm + 1e-6)); scale / max_norm / norm / coef: one-element
-    device float tensors (views)."""
+    device float tensors (views).  ok (int32 [1]), skipped (int64 [1]): the finalize also decides the step, ok = isfinite(norm),
+    skipped += 1 when not (coef required)."""
+    if ok is not None:
+        _call("mmfn_grad_norm_finalize_guard", ptr(partials), partials.numel(), ptr(scale), ptr(max_norm), ptr(norm), ptr(coef),
+              ptr(ok), ptr(skipped), stream())
+        return
     _call("mmfn_grad_norm_finalize", ptr(partials), partials.numel(), ptr(scale), ptr(max_norm), ptr(norm), ptr(coef), stream())
-
-
-def grad_norm_finalize_guard(partials, scale, max_norm, norm, coef, ok, skipped):
-    """grad_norm_finalize that also decides the step: ok (int32 [1]) = isfinite(norm), skipped (int64 [1]) += 1 when not."""
-    _call("mmfn_grad_norm_finalize_guard", ptr(partials), partials.numel(), ptr(scale), ptr(max_norm), ptr(norm), ptr(coef), ptr(ok),
-          ptr(skipped), stream())
 
 
 def copy_if(dst, src, flag, when):

@@ -55,11 +55,11 @@ def test_guarded_kernels_take_a_finite_step_bitwise_and_skip_a_non_finite_one(n,
         skipped = torch.zeros(1, dtype=torch.int64, device=DEV)
         step = torch.full((1,), 3, dtype=torch.int64, device=DEV)
         on_skip, on_take = torch.zeros(n, device=DEV), torch.zeros(n, device=DEV)
-        ops.grad_norm_finalize_guard(_partials(g), scale, max_norm, out[0:1], out[1:2], ok, skipped)
-        ops.step_advance_if(step, ok)
+        ops.grad_norm_finalize(_partials(g), scale, max_norm, out[0:1], out[1:2], ok=ok, skipped=skipped)
+        ops.step_advance(step, ok=ok)
         ops.copy_if(on_skip, src, ok, when=False)
         ops.copy_if(on_take, src, ok, when=True)
-        ops.adamw_groups_coef(q, g, mm, vv, step, hyper, groups, out[1:2], group_of=group_of, ok=ok)
+        ops.adamw_groups(q, g, mm, vv, step, hyper, groups, group_of=group_of, coef=out[1:2], ok=ok)
         torch.cuda.synchronize()
         return q, mm, vv, out, int(ok.item()), int(skipped.item()), int(step.item()), on_skip, on_take
 
@@ -69,7 +69,7 @@ def test_guarded_kernels_take_a_finite_step_bitwise_and_skip_a_non_finite_one(n,
     rstep = torch.full((1,), 3, dtype=torch.int64, device=DEV)
     ops.grad_norm_finalize(_partials(g), scale, max_norm, rout[0:1], rout[1:2])
     ops.step_advance(rstep)
-    ops.adamw_groups_coef(rp, g, rm, rv, rstep, hyper, groups, rout[1:2], group_of=group_of)
+    ops.adamw_groups(rp, g, rm, rv, rstep, hyper, groups, group_of=group_of, coef=rout[1:2])
     q, mm, vv, out, ok, skipped, step, on_skip, on_take = guarded(g)
     assert float(rout[1].item()) < 1.0 and not torch.equal(rp, p)
     assert torch.equal(q, rp) and torch.equal(mm, rm) and torch.equal(vv, rv) and torch.equal(out, rout)
@@ -108,11 +108,12 @@ def test_guarded_kernels_refuse_null_or_misaligned_arguments():
     assert L.mmfn_step_advance_if(None, P(ok), s) == -1 and L.mmfn_step_advance_if(P(i64), None, s) == -1
     assert L.mmfn_step_advance_if(P(i64, 4), P(ok), s) == -1 and L.mmfn_step_advance_if(P(i64), P(ok, 2), s) == -1
 
-    adam = lambda **k: L.mmfn_adamw_groups_guard_f32(k.get("p", P(p)), P(g), P(m), P(v), k.get("n", 64), None, P(hyper), 1, P(i64),
-                                                     k.get("coef", P(out)), k.get("ok", P(ok)), s)
+    COEF, AVG, GUARD = 1, 2, 4   # the variant bits of mmfn_adamw_groups_f32 (include/mmfn_hip.h)
+    adam = lambda **k: L.mmfn_adamw_groups_f32(k.get("p", P(p)), P(g), P(m), P(v), k.get("n", 64), None, P(hyper), 1, P(i64),
+                                               COEF | GUARD, k.get("coef", P(out)), None, None, None, 0, k.get("ok", P(ok)), s)
     assert adam(ok=None) == -1 and adam(ok=P(ok, 1)) == -1 and adam(coef=None) == -1 and adam(p=P(p, 4)) == -1 and adam(n=62) == -1
-    adam_avg = lambda **k: L.mmfn_adamw_groups_guard_avg_f32(P(p), P(g), P(m), P(v), 64, None, P(hyper), 1, P(i64), P(out),
-                                                             k.get("avg", P(avg)), P(i64, 8), P(out, 4), 0, k.get("ok", P(ok)), s)
+    adam_avg = lambda **k: L.mmfn_adamw_groups_f32(P(p), P(g), P(m), P(v), 64, None, P(hyper), 1, P(i64), COEF | AVG | GUARD, P(out),
+                                                   k.get("avg", P(avg)), P(i64, 8), P(out, 4), 0, k.get("ok", P(ok)), s)
     assert adam_avg(ok=None) == -1 and adam_avg(avg=P(avg, 4)) == -1 and adam_avg(avg=None) == -1
     wavg = lambda **k: L.mmfn_weight_average_if_f32(k.get("avg", P(avg)), k.get("src", P(p)), k.get("n", 64), P(i64), P(out), 0,
                                                     k.get("ok", P(ok)), s)
@@ -130,6 +131,62 @@ def test_guarded_kernels_refuse_null_or_misaligned_arguments():
     assert st(out=None) == -1 and st(out=P(part, 4)) == -1 and st(ws=None) == -1 and st(n=0) == -1 and st(chunks=0) == -1
     assert st() == 0
     torch.cuda.synchronize()
+
+
+def test_adamw_groups_refuses_variants_without_an_instance_and_a_bad_average():
+    from mmfn_amd import ops
+    from mmfn_amd._lib import lib
+    L = lib()
+    f = lambda: torch.zeros(64, device=DEV)
+    p, g, m, v, avg, hyper = f(), f(), f(), f(), f(), torch.zeros(16, 8, device=DEV)
+    hyper[0, :6] = torch.tensor([1e-3, 0.9, 0.999, 1e-8, 1e-2, 1.0])
+    step, cnt = torch.ones(1, dtype=torch.int64, device=DEV), torch.zeros(1, dtype=torch.int64, device=DEV)
+    coef, w = torch.ones(1, device=DEV), torch.zeros(1, device=DEV)
+    ok = torch.ones(1, dtype=torch.int32, device=DEV)
+    s = torch.cuda.current_stream().cuda_stream
+    COEF, AVG, GUARD = ops.ADAMW_COEF, ops.ADAMW_AVG, ops.ADAMW_GUARD
+    assert (COEF, AVG, GUARD) == (1, 2, 4)
+
+    def adam(variant, mode=ops.AVG_EMA, ema_w=w.data_ptr()):   # every pointer given and legal unless the case withholds it
+        return L.mmfn_adamw_groups_f32(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), 64, None, hyper.data_ptr(), 1,
+                                       step.data_ptr(), variant, coef.data_ptr(), avg.data_ptr(), cnt.data_ptr(), ema_w, mode,
+                                       ok.data_ptr(), s)
+
+    for variant in (GUARD, AVG | GUARD, 8, -1):
+        assert adam(variant) == -1, variant
+    assert adam(COEF | AVG | GUARD, mode=7) == -1
+    assert adam(AVG, mode=ops.AVG_EMA, ema_w=None) == -1
+    assert adam(AVG, mode=ops.AVG_SWA, ema_w=None) == 0
+    for variant in (0, COEF, AVG, COEF | AVG, COEF | GUARD, COEF | AVG | GUARD):   # the six instances that exist
+        assert adam(variant) == 0, variant
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("groups", [1, 3])
+@pytest.mark.parametrize("n", [4, 4 * 1021])     # one float4 in one lane; a partial last wave
+def test_guarded_averaging_adamw_is_the_unguarded_launch_when_ok_and_touches_nothing_otherwise(n, groups):
+    from mmfn_amd import ops
+    p, g, m, v, hyper, group_of = _flat_case(n, groups)
+    a = torch.randn(n, device=DEV)
+    step = torch.full((1,), 3, dtype=torch.int64, device=DEV)
+    coef, w = torch.tensor([0.37], device=DEV), torch.tensor([0.1], device=DEV)
+    flag = {x: torch.full((1,), x, dtype=torch.int32, device=DEV) for x in (0, 1)}
+
+    def run(avg_args, ok):
+        q, mm, vv, aa = p.clone(), m.clone(), v.clone(), a.clone()
+        ops.adamw_groups(q, g, mm, vv, step, hyper, groups, group_of=group_of, coef=coef, avg=(aa,) + avg_args, ok=ok)
+        return q, mm, vv, aa
+
+    for mode in (ops.AVG_EMA, ops.AVG_SWA):
+        for k in (0, 2):
+            avg_args = (torch.tensor([k], dtype=torch.int64, device=DEV), w, mode)
+            ref, taken, skipped = run(avg_args, None), run(avg_args, flag[1]), run(avg_args, flag[0])
+            torch.cuda.synchronize()
+            assert not torch.equal(ref[0], p) and (torch.equal(ref[3], ref[0]) if k == 0 else not torch.equal(ref[3], ref[0]))
+            for x, y in zip(taken, ref):
+                assert torch.equal(x, y), (mode, k)
+            for x, y in zip(skipped, (p, m, v, a)):
+                assert torch.equal(x, y), (mode, k)
 
 
 # ------------------------------------------------------------------------------------------------ per-tensor statistics

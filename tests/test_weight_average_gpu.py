@@ -87,16 +87,18 @@ def test_kernels_refuse_misaligned_ragged_or_null_arguments():
     step = torch.ones(1, dtype=torch.int64, device=DEV)
     coef = torch.ones(1, device=DEV)
     args = (b.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), 64, None, hyper.data_ptr(), 1, step.data_ptr())
-    assert L.mmfn_adamw_groups_avg_f32(*args, a[1:].data_ptr(), cnt.data_ptr(), w.data_ptr(), E, s) == -1
-    assert L.mmfn_adamw_groups_avg_f32(*args, a.data_ptr(), None, w.data_ptr(), E, s) == -1
-    assert L.mmfn_adamw_groups_coef_avg_f32(*args, None, a.data_ptr(), cnt.data_ptr(), w.data_ptr(), E, s) == -1
-    assert L.mmfn_adamw_groups_coef_avg_f32(*args, coef.data_ptr(), a.data_ptr(), cnt.data_ptr(), w.data_ptr(), 3, s) == -1
-    assert L.mmfn_adamw_groups_avg_f32(*args, a.data_ptr(), cnt.data_ptr(), w.data_ptr(), E, s) == 0
+    adam = L.mmfn_adamw_groups_f32   # (..., variant, coef, avg, n_averaged, ema_w, avg_mode, ok, stream)
+    AVG, COEF_AVG = ops.ADAMW_AVG, ops.ADAMW_COEF | ops.ADAMW_AVG
+    assert adam(*args, AVG, None, a[1:].data_ptr(), cnt.data_ptr(), w.data_ptr(), E, None, s) == -1
+    assert adam(*args, AVG, None, a.data_ptr(), None, w.data_ptr(), E, None, s) == -1
+    assert adam(*args, COEF_AVG, None, a.data_ptr(), cnt.data_ptr(), w.data_ptr(), E, None, s) == -1
+    assert adam(*args, COEF_AVG, coef.data_ptr(), a.data_ptr(), cnt.data_ptr(), w.data_ptr(), 3, None, s) == -1
+    assert adam(*args, AVG, None, a.data_ptr(), cnt.data_ptr(), w.data_ptr(), E, None, s) == 0
     torch.cuda.synchronize()
 
 
 @pytest.mark.parametrize("mode", ["ema", "swa"])
-def test_fused_adamw_average_equals_plain_step_then_standalone_average(mode):
+def test_fused_average_adamw_equals_plain_step_then_standalone_average(mode):
     from mmfn_amd import ops
     n = 4 * 300007
     gen = torch.Generator(device=DEV).manual_seed(7)
@@ -117,13 +119,10 @@ def test_fused_adamw_average_equals_plain_step_then_standalone_average(mode):
         for k in (0, 2):
             cnt = torch.tensor(k, dtype=torch.int64, device=DEV)
             p1, m1, v1, a1 = p0.clone(), m0.clone(), v0.clone(), a0.clone()
-            if clip is None:
-                ops.adamw_groups(p1, g, m1, v1, step, hyper, 2, group_of=group_of)
-            else:
-                ops.adamw_groups_coef(p1, g, m1, v1, step, hyper, 2, clip, group_of=group_of)
+            ops.adamw_groups(p1, g, m1, v1, step, hyper, 2, group_of=group_of, coef=clip)
             ops.weight_average(a1, p1, cnt, w, code)
             p2, m2, v2, a2 = p0.clone(), m0.clone(), v0.clone(), a0.clone()
-            ops.adamw_groups_avg(p2, g, m2, v2, step, hyper, 2, a2, cnt, w, code, group_of=group_of, coef=clip)
+            ops.adamw_groups(p2, g, m2, v2, step, hyper, 2, group_of=group_of, coef=clip, avg=(a2, cnt, w, code))
             torch.cuda.synchronize()
             for x, y in ((p1, p2), (m1, m2), (v1, v2), (a1, a2)):
                 assert torch.equal(x, y), (clip is not None, k)
