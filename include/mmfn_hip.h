@@ -527,17 +527,23 @@ int mmfn_weight_average_f32(float* avg, const float* src, int64_t n, const int64
  * {lr, beta1, beta2, eps, weight_decay, grad_scale, 0, 0}; group_of: one group id per 4 consecutive parameters (tensors
  * of the flat layout are 16-byte aligned), NULL = all group 0; n must be a multiple of 4; n_groups <= 16.
  * The bits of `variant` select the kernel instance; a set bit makes its pointers mandatory (else
- * MMFN_EINVAL), the pointers of a clear bit are ignored.  Valid: 0, COEF, AVG, COEF|AVG, COEF|GUARD, COEF|AVG|GUARD; anything else
- * is MMFN_EINVAL.
+ * MMFN_EINVAL), the pointers of a clear bit are ignored.  Valid: 0, COEF, AVG, COEF|AVG, COEF|GUARD, COEF|AVG|GUARD, each with
+ * or without MASK; anything else is MMFN_EINVAL.
  *   COEF   every group's grad_scale is multiplied by *coef (device memory: the clip coefficient of mmfn_grad_norm_finalize, so
  *          clipping needs no host round trip and stays inside a captured hipGraph)
  *   AVG    each NEW parameter is also folded into avg[0, n) as mmfn_weight_average_f32 does (one pass: +8 B per parameter);
  *          avg, n_averaged, ema_w, avg_mode as there
  *   GUARD  the whole launch sits behind *ok (int32 in device memory, 4-byte aligned: the non-finite guard's flag of
- *          mmfn_grad_norm_finalize_guard): bit-identical to the unguarded instance when *ok, no access at all otherwise */
+ *          mmfn_grad_norm_finalize_guard): bit-identical to the unguarded instance when *ok, no access at all otherwise
+ *   MASK   frozen parameters (requires_grad = False): a float4 whose group_of byte is MMFN_ADAMW_FROZEN neither loads nor stores
+ *          p / m / v - no step, no weight decay, as torch skips a parameter without a gradient; with AVG it loads p alone and
+ *          the average is still updated from it.  group_of is mandatory, also with one group.  Every other float4 gets the bits
+ *          of the instance without MASK */
 #define MMFN_ADAMW_COEF 1
 #define MMFN_ADAMW_AVG 2
 #define MMFN_ADAMW_GUARD 4
+#define MMFN_ADAMW_MASK 8
+#define MMFN_ADAMW_FROZEN 255 /* group_of byte of a frozen float4 (MASK) */
 int mmfn_adamw_groups_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of, const float* hyper,
                           int n_groups, const int64_t* step, int variant, const float* coef, float* avg, const int64_t* n_averaged,
                           const float* ema_w, int avg_mode, const int32_t* ok, void* stream);
@@ -580,6 +586,14 @@ int mmfn_copy_if(void* dst, const void* src, int64_t nbytes, const int32_t* flag
 int mmfn_tensor_stats_chunk(void);
 int mmfn_tensor_stats_f32(const float* flat, const int64_t* table, int n_tensors, int64_t n_chunks, float scale, double* out,
                           double* workspace, void* stream);
+/* flat[offset, offset + count) = value for every range of `table` (the format above; here every count is a multiple of 4 and the
+ * ranges do not overlap): one launch, one workgroup per chunk, float4 stores that stay inside their range.  It keeps the gradient
+ * ranges of frozen parameters at zero.  flat 16-byte aligned, table 8, n_chunks >= n_ranges >= 1, else MMFN_EINVAL. */
+int mmfn_fill_ranges_f32(float* flat, const int64_t* table, int n_ranges, int64_t n_chunks, float value, void* stream);
+/* *slot (fp64, device memory, 8-byte aligned) = NaN when any of x[0, n) is not finite, else 0.0: an extra entry of the partials
+ * table of mmfn_grad_norm_finalize_guard, so that a guarded step with frozen BatchNorm layers is also skipped when the forward
+ * left non-finite running statistics.  One workgroup.  x 4-byte aligned, n >= 1, else MMFN_EINVAL. */
+int mmfn_nonfinite_slot_f32(const float* x, int64_t n, double* slot, void* stream);
 
 /* ---- sensor ingest (dataloader.py:271-308, model_vec.py:33-44,368-381) ------------------------- */
 int mmfn_ingest_rgb_u8(const uint8_t* in, float* out, int B, int H, int W, int crop, void* stream);

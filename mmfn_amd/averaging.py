@@ -9,6 +9,8 @@ variant and config, so `.module` is validated, checkpointed and deployed like th
     AdamW launch (mmfn_adamw_groups_f32 with MMFN_ADAMW_AVG), eager or graph-replayed.
 The weight is formed as torch forms it (EMA: fp32(1 - decay) from a Python float; SWA: 1 / (n_averaged + 1) in fp32 on the
 device), the first update copies, and both n_averaged and the EMA weight live in device memory (a captured step stays valid).
+Frozen parameters (requires_grad = False) are averaged like the others, as AveragedModel does: the masked AdamW launch skips
+their step and their moments but still loads them and updates the average (MMFN_ADAMW_MASK with MMFN_ADAMW_AVG).
 """
 import copy
 

@@ -118,8 +118,11 @@ __device__ inline f32x4 lerp4(f32x4 a, f32x4 p, float w) {
 // mmfn_grad_norm_finalize); COEF = false is the plain grouped step.  AVG: the new parameter is also folded into avg.avg
 // (the weight average), from registers: 8 B more per parameter instead of a 12 B pass of its own.  GUARD (with COEF only): *ok
 // is the non-finite guard's flag (mmfn_grad_norm_finalize_guard); when it is 0 the whole grid returns before it reads or writes
-// anything, so parameters, moments and the average keep their bits
-template <bool COEF, bool AVG, bool GUARD>
+// anything, so parameters, moments and the average keep their bits.  MASK: a float4 whose group_of byte is MMFN_ADAMW_FROZEN
+// belongs to a parameter that is not trained (requires_grad = False): torch skips such a parameter entirely, so the float4 neither
+// loads nor stores p / m / v (no weight decay either); with AVG it loads p alone and the average still follows it, as AveragedModel
+// lerps every parameter.  A template bit and not a branch of the other instances: they keep their code
+template <bool COEF, bool AVG, bool GUARD, bool MASK>
 __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                            float* __restrict__ v, int64_t n, const uint8_t* __restrict__ group_of,
                                                            const float* __restrict__ hyper, int n_groups,
@@ -141,6 +144,15 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p
   __syncthreads();
   const int64_t n4 = (n + 3) >> 2;   // the flat buffers are padded to a multiple of 4 floats
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    if (MASK && group_of[i] == MMFN_ADAMW_FROZEN) {
+      if (AVG) {
+        const f32x4 pf = *reinterpret_cast<const f32x4*>(p + i * 4);
+        f32x4 out = pf;
+        if (*avg.n_averaged != 0) out = lerp4(*reinterpret_cast<const f32x4*>(avg.avg + i * 4), pf, avg_weight(avg));
+        *reinterpret_cast<f32x4*>(avg.avg + i * 4) = out;
+      }
+      continue;
+    }
     const GroupScalars s = gs[group_of ? group_of[i] : 0];
     f32x4 pv = *reinterpret_cast<f32x4*>(p + i * 4);
     f32x4 gv = *reinterpret_cast<const f32x4*>(g + i * 4);
@@ -199,14 +211,17 @@ bool avg_args_ok(const AvgArgs& a) {
 bool flag_ok(const int32_t* ok) { return ok && !((uintptr_t)ok & 3); }   // the non-finite guard's device flag
 }  // namespace
 
-// One entry point for the six instances of adamw_groups_kernel: the bits of `variant` (MMFN_ADAMW_COEF | _AVG | _GUARD) are the
+// One entry point for the instances of adamw_groups_kernel: the bits of `variant` (MMFN_ADAMW_COEF | _AVG | _GUARD | _MASK) are the
 // template arguments.  A set bit makes its pointers mandatory; the pointers of a clear bit are ignored.
 namespace {
-using AdamwGroupsKernel = decltype(&adamw_groups_kernel<false, false, false>);
-const AdamwGroupsKernel kAdamwGroups[8] = {   // by variant; nullptr: GUARD without COEF, which is not built
-    adamw_groups_kernel<false, false, false>, adamw_groups_kernel<true, false, false>, adamw_groups_kernel<false, true, false>,
-    adamw_groups_kernel<true, true, false>,   nullptr, adamw_groups_kernel<true, false, true>, nullptr,
-    adamw_groups_kernel<true, true, true>};
+using AdamwGroupsKernel = decltype(&adamw_groups_kernel<false, false, false, false>);
+#define MMFN_ADAMW_ROW(MASK)                                                                                                    \
+  adamw_groups_kernel<false, false, false, MASK>, adamw_groups_kernel<true, false, false, MASK>,                                \
+      adamw_groups_kernel<false, true, false, MASK>, adamw_groups_kernel<true, true, false, MASK>, nullptr,                     \
+      adamw_groups_kernel<true, false, true, MASK>, nullptr, adamw_groups_kernel<true, true, true, MASK>
+const AdamwGroupsKernel kAdamwGroups[16] = {   // by variant; nullptr: GUARD without COEF, which is not built
+    MMFN_ADAMW_ROW(false), MMFN_ADAMW_ROW(true)};
+#undef MMFN_ADAMW_ROW
 }  // namespace
 
 extern "C" int mmfn_adamw_groups_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of,
@@ -214,11 +229,12 @@ extern "C" int mmfn_adamw_groups_f32(float* p, const float* g, float* m, float* 
                                      float* avg, const int64_t* n_averaged, const float* ema_w, int avg_mode, const int32_t* ok,
                                      void* stream) {
   if (n <= 0) return 0;
-  if (variant < 0 || variant >= 8 || !kAdamwGroups[variant]) return MMFN_EINVAL;
+  if (variant < 0 || variant >= 16 || !kAdamwGroups[variant]) return MMFN_EINVAL;
   const bool with_coef = variant & MMFN_ADAMW_COEF, with_avg = variant & MMFN_ADAMW_AVG, guard = variant & MMFN_ADAMW_GUARD;
+  const bool mask = variant & MMFN_ADAMW_MASK;
   const AvgArgs a = with_avg ? AvgArgs{avg, n_averaged, ema_w, avg_mode} : AvgArgs{};
   if (!adamw_args_ok(p, g, m, v, n, hyper, n_groups, step) || (with_coef && !coef) || (with_avg && !avg_args_ok(a)) ||
-      (guard && !flag_ok(ok)))
+      (guard && !flag_ok(ok)) || (mask && !group_of))
     return MMFN_EINVAL;
   hipLaunchKernelGGL(kAdamwGroups[variant], dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, group_of, hyper,
                      n_groups, step, with_coef ? coef : nullptr, a, guard ? ok : nullptr);
@@ -507,6 +523,63 @@ extern "C" int mmfn_tensor_stats_f32(const float* flat, const int64_t* table, in
   const hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(tensor_stats_chunk_kernel, dim3((unsigned)n_chunks), dim3(kAccumThreads), 0, st, flat, table, n_tensors, workspace);
   hipLaunchKernelGGL(tensor_stats_combine_kernel, dim3(n_tensors), dim3(kAccumThreads), 0, st, table, n_chunks, workspace, scale, out);
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- one value over a set of ranges of a flat buffer ---------------------------------------------------------------------------
+// The gradient ranges of frozen parameters are kept at +0.0 (a fused backward launch may write a frozen tensor's gradient as a
+// byproduct): one launch per readiness group stores `value` over the group's frozen ranges.  The table has the format of
+// mmfn_tensor_stats_f32 - (offset, count, first chunk), one workgroup per chunk of kStatsChunk floats - with counts that are
+// multiples of 4, so every store is a whole float4 inside its range.
+namespace {
+__global__ __launch_bounds__(kAccumThreads) void fill_ranges_kernel(float* __restrict__ flat, const int64_t* __restrict__ table,
+                                                                    int n_ranges, float value) {
+  const int64_t c = blockIdx.x;
+  int lo = 0, hi = n_ranges - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (table[mid * 3 + 2] <= c) lo = mid; else hi = mid - 1;
+  }
+  const int64_t count = table[lo * 3 + 1];
+  const int64_t base = (c - table[lo * 3 + 2]) * kStatsChunk;
+  float* x = flat + table[lo * 3 + 0];
+  const f32x4 val{value, value, value, value};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int64_t i = base + ((int64_t)j * kAccumThreads + threadIdx.x) * 4;
+    if (i + 4 <= count) *reinterpret_cast<f32x4*>(x + i) = val;
+  }
+}
+}  // namespace
+
+// ---- the guard over frozen BatchNorm layers ---------------------------------------------------------------------------------
+// *slot = NaN when any of x[0, n) is not finite, else 0.0: one more entry of the gradient-norm partials table.  With frozen
+// trunks the backward that would have carried a non-finite activation into the gradient is not run (and a ReLU drops a NaN), so
+// the guarded step also looks at what the forward left in the BatchNorm running statistics.  One workgroup: n is tens of thousands.
+namespace {
+__global__ __launch_bounds__(kAccumThreads) void nonfinite_slot_kernel(const float* __restrict__ x, int64_t n, double* __restrict__ slot) {
+  double bad = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += kAccumThreads)
+    if (!finite_f32(x[i])) bad += 1.0;
+  const double t = block_sum_f64(bad);
+  if (threadIdx.x == 0) *slot = t > 0.0 ? __longlong_as_double(0x7ff8000000000000LL) : 0.0;
+}
+}  // namespace
+
+extern "C" int mmfn_nonfinite_slot_f32(const float* x, int64_t n, double* slot, void* stream) {
+  if (!x || ((uintptr_t)x & 3) || n < 1 || !slot || ((uintptr_t)slot & 7)) return MMFN_EINVAL;
+  hipLaunchKernelGGL(nonfinite_slot_kernel, dim3(1), dim3(kAccumThreads), 0, (hipStream_t)stream, x, n, slot);
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mmfn_fill_ranges_f32(float* flat, const int64_t* table, int n_ranges, int64_t n_chunks, float value, void* stream) {
+  if (!flat || ((uintptr_t)flat & 15) || !table || ((uintptr_t)table & 7) || n_ranges < 1 || n_chunks < n_ranges ||
+      n_chunks > 0x7fffffff)
+    return MMFN_EINVAL;
+  hipLaunchKernelGGL(fill_ranges_kernel, dim3((unsigned)n_chunks), dim3(kAccumThreads), 0, (hipStream_t)stream, flat, table, n_ranges,
+                     value);
   MMFN_LAUNCH_CHECK();
   return 0;
 }

@@ -12,6 +12,7 @@ around each GPT (model_vec.py:228,240-244) do not exist here.
 Backward conventions: `bwd` methods receive dL/d(output) buffers and write parameter gradients
 straight into the flat gradient buffer (each parameter has exactly one writer per step).
 """
+import contextlib
 import math
 
 import os
@@ -60,6 +61,8 @@ class Ctx(object):
         self.adt = engine.act_dtype if engine is not None else torch.float32   # dtype of activation / activation-gradient buffers
         self.bf16 = self.adt == torch.bfloat16
         self.folded = False  # eval forward over BatchNorm-folded filters (Engine.fold_batchnorm)
+        # fz(*gradient views): every one of them belongs to a frozen parameter, so a launch that only writes them is not issued
+        self.fz = engine.fz if engine is not None else (lambda *g: False)
 
     def wino_u(self, name, w):
         """Engine-wide buffer for a layer's transformed filter U [36][Co][Ci]; registers the layer for the grouped transform."""
@@ -228,6 +231,8 @@ class ConvBN(object):
         K = KH * KW * Ci
         col = self.saved_col
         KP = col.shape[1]
+        if ctx.fz(self.gw):   # frozen filter: no weight gradient
+            return
         dwp = ctx.bufs.get(self.name + ".dwpad", (Co, KP))
         ops.linear_dw(dco.view(-1, Co), col, out=dwp)
         ops.repitch_rows(dwp, self.gw, Co, K, KP, K)
@@ -241,7 +246,7 @@ class ConvBN(object):
         ops.stem_bn_bwd_pooled(g, idx, co, mean, rstd, self.bn_w, self.bn_b, dco, self.g_bn_w, self.g_bn_b)
         if self.is_stem():
             self.stem_wgrad(ctx, dco)
-        else:
+        elif not ctx.fz(self.gw):
             ops.conv2d_wgrad(dco, x, tuple(self.w.shape), self.stride, self.pad, out=self.gw, v=getattr(self, "saved_v", None))
 
     def fwd16(self, ctx, x, relu=True, res=None, lazy=False):
@@ -344,10 +349,11 @@ class ConvBN(object):
         if x.dtype == torch.float32:   # stem: no data gradient
             if self.is_stem():
                 self.stem_wgrad(ctx, dco)
-            else:
+            elif not ctx.fz(self.gw):
                 ops.conv2d_wgrad(dco, x, tuple(self.w.shape), self.stride, self.pad, out=self.gw)
             return None
-        ops16.conv2d_wgrad(dco, x, tuple(self.w.shape), self.stride, self.pad, self.gw)
+        if not ctx.fz(self.gw):
+            ops16.conv2d_wgrad(dco, x, tuple(self.w.shape), self.stride, self.pad, self.gw)
         if not need_dx:
             return None
         dx = ctx.bufs.get(self.name + ".dx", x.shape, ctx.adt)
@@ -474,7 +480,7 @@ class ConvBN(object):
             ops.bn_bwd_reduce(g.view(M, self.cout), ymask, co.view(M, self.cout), mean, rstd, self.g_bn_w, self.g_bn_b, means,
                               relu_wb=None if relu_bias is None else (self.bn_w, relu_bias))
             dx = ctx.bufs.get(self.name + ".dx", x.shape)
-            ops.conv2d_bwd_winograd(dco, x, u, self.gw, dx, v=getattr(self, "saved_v", None), res=dx_res,
+            ops.conv2d_bwd_winograd(dco, x, u, None if ctx.fz(self.gw) else self.gw, dx, v=getattr(self, "saved_v", None), res=dx_res,
                                     bn=(g, None if ymask is None else ymask.view(g.shape), co, mean, rstd, self.bn_w, relu_bias, means,
                                         ge_out))
             return dx
@@ -484,7 +490,8 @@ class ConvBN(object):
         if self.is_stem() and not need_dx:
             self.stem_wgrad(ctx, dco)
             return None
-        ops.conv2d_wgrad(dco, x, tuple(self.w.shape), self.stride, self.pad, out=self.gw, v=getattr(self, "saved_v", None))
+        if not ctx.fz(self.gw):
+            ops.conv2d_wgrad(dco, x, tuple(self.w.shape), self.stride, self.pad, out=self.gw, v=getattr(self, "saved_v", None))
         if not need_dx:
             return None
         dx = ctx.bufs.get(self.name + ".dx", x.shape)
@@ -626,7 +633,7 @@ class LayerNorm(object):
             part = ctx.bufs.get(self.name + ".part", (rows, 3 if colsum is not None else 2, C))
             ops.layernorm_bwd_partial(g, x, self.w, self.b, mean, rstd, dx, part, act, dres=dres, dx_dropped=dropped, drop_p=drop_p,
                                       rng_state=rng, rng_stream=rng_stream, want_colsum=colsum is not None)
-            fin = lambda: ops.layernorm_bwd_finalize(part, rows, C, self.gw, self.gb, colsum)
+            fin = lambda: _ln_finalize(ctx, part, rows, C, self.gw, self.gb, colsum)
             if collect is not None:
                 collect.append((part, self.gw, self.gb, colsum, rows, C))   # GPT.bwd: one batched launch for all of them at its end
             elif isinstance(defer, list):
@@ -655,13 +662,29 @@ SIDE_SPLIT_MAX_C = 256
 # chain (ops.gpt_block_*, csrc/gpt_block.hip): step 31.00 -> 29.98 ms.
 
 
-def _dw_db(dy, x, gw, gb):
+def _dw_db(ctx, dy, x, gw, gb):
     """A Linear's weight AND bias gradient: one GEMM in fp32 (the bias gradient = the column sums of dy, formed from the operand
-    fragments of dW = dy^T x: MMFN_EPI_COLSUM_A), column sums + GEMM in the bf16 mode."""
+    fragments of dW = dy^T x: MMFN_EPI_COLSUM_A), column sums + GEMM in the bf16 mode.  Both frozen: no launch; one of them: the
+    launch runs as it is and the frozen range is zeroed behind it (Engine._ready)."""
+    if ctx.fz(gw, gb):
+        return None
     if dy.dtype == torch.bfloat16:
         ops.colsum(dy, gb)
         return ops.linear_dw(dy, x, out=gw)
     return ops.linear_dw(dy, x, out=gw, db=gb)
+
+
+def _dw(ctx, dy, x, gw):
+    """A Linear's weight gradient alone (its bias gradient comes out of a LayerNorm backward); none for a frozen weight."""
+    if not ctx.fz(gw):
+        ops.linear_dw(dy, x, out=gw)
+
+
+def _ln_finalize(ctx, part, rows, C, gw, gb, colsum):
+    """The row reduction of a LayerNorm backward's partials into its weight / bias gradient (+ the consuming Linear's bias
+    gradient); not issued when all of them are frozen."""
+    if not ctx.fz(*[t for t in (gw, gb, colsum) if t is not None]):
+        ops.layernorm_bwd_finalize(part, rows, C, gw, gb, colsum)
 
 
 class GPT(object):
@@ -871,13 +894,13 @@ class GPT(object):
             gp, gp2 = (GD[i] if drop else G[i]), (GD2[i] if drop else G1[i])
             below_gb = self.blocks[i - 1]["fc2"].gb if i > 0 else None
             side += [
-                lambda gp=gp, blk=blk, h=h: ops.linear_dw(gp, h, out=blk["fc2"].gw),
-                lambda gh=GH[i], blk=blk, a2=a2: _dw_db(gh, a2, blk["fc1"].gw, blk["fc1"].gb),
-                lambda p=P2[i], blk=blk: ops.layernorm_bwd_finalize(p, nrow, C, blk["ln2"].gw, blk["ln2"].gb, blk["proj"].gb),
-                lambda gp2=gp2, blk=blk, o=o: ops.linear_dw(gp2, o, out=blk["proj"].gw),
-                lambda dqkv=dqkv, blk=blk, a=a: _dw_db(dqkv, a, blk["g_wqkv"], blk["g_bqkv"]),
+                lambda gp=gp, blk=blk, h=h: _dw(ctx, gp, h, blk["fc2"].gw),
+                lambda gh=GH[i], blk=blk, a2=a2: _dw_db(ctx, gh, a2, blk["fc1"].gw, blk["fc1"].gb),
+                lambda p=P2[i], blk=blk: _ln_finalize(ctx, p, nrow, C, blk["ln2"].gw, blk["ln2"].gb, blk["proj"].gb),
+                lambda gp2=gp2, blk=blk, o=o: _dw(ctx, gp2, o, blk["proj"].gw),
+                lambda dqkv=dqkv, blk=blk, a=a: _dw_db(ctx, dqkv, a, blk["g_wqkv"], blk["g_bqkv"]),
                 lambda p=(P1[i] if i > 0 else P1[i].view(-1)[:nrow * 2 * C].view(nrow, 2, C)), blk=blk, cs=below_gb:
-                    ops.layernorm_bwd_finalize(p, nrow, C, blk["ln1"].gw, blk["ln1"].gb, cs),
+                    _ln_finalize(ctx, p, nrow, C, blk["ln1"].gw, blk["ln1"].gb, cs),
             ]
             work, side = side, []
             pending = (ctx.fork_point(), work)
@@ -951,7 +974,7 @@ class GPT(object):
             x, a, qkv, o, lse, x1, a2, h = self.acts[i]
             # ---- MLP branch: x2 = x1 + drop(fc2(relu(fc1(ln2(x1)))))
             gp = GD[i] if drop else g
-            side.append(lambda gp=gp, blk=blk, h=h: ops.linear_dw(gp, h, out=blk["fc2"].gw))   # fc2.gb: from the LayerNorm backward
+            side.append(lambda gp=gp, blk=blk, h=h: _dw(ctx, gp, h, blk["fc2"].gw))   # fc2.gb: from the LayerNorm backward
             gh = GH[i]
             ghpart = None
             if ctx.bf16:
@@ -967,23 +990,23 @@ class GPT(object):
                 pending = None
             if ghpart is not None:
                 side.append(lambda gh=gh, blk=blk, a2=a2, p=ghpart, r=ghrows: (ops16.colsum_partials(p, r, 4 * C, blk["fc1"].gb),
-                                                                               ops.linear_dw(gh, a2, out=blk["fc1"].gw)))
+                                                                               _dw(ctx, gh, a2, blk["fc1"].gw)))
             else:
-                side.append(lambda gh=gh, blk=blk, a2=a2: _dw_db(gh, a2, blk["fc1"].gw, blk["fc1"].gb))
+                side.append(lambda gh=gh, blk=blk, a2=a2: _dw_db(ctx, gh, a2, blk["fc1"].gw, blk["fc1"].gb))
             ga2 = bufs.get(nm + ".ga", (M, C), adt)
             ops.linear_dx(gh, Wb(blk["fc1"]), out=ga2)
             g1 = blk["ln2"].bwd(ctx, ga2, dres=g, out=G1[i], dropped=GD2[i] if drop else None, drop_p=p_resid,
                                 rng_stream=sb + 1, colsum=blk["proj"].gb, defer=side, collect=fins)
             # ---- attention branch: x1 = x + drop(proj(att(ln1(x))))
             gp = GD2[i] if drop else g1
-            side.append(lambda gp=gp, blk=blk, o=o: ops.linear_dw(gp, o, out=blk["proj"].gw))   # proj.gb: from ln2's backward
+            side.append(lambda gp=gp, blk=blk, o=o: _dw(ctx, gp, o, blk["proj"].gw))   # proj.gb: from ln2's backward
             go = bufs.get(nm + ".go", (M, C), adt)
             ops.linear_dx(gp, Wb(blk["proj"]), out=go)
             dqkv = DQKV[i]
             delta = bufs.get(nm + ".delta", (B, nh, T))
             ops.attention_bwd(qkv[:, C:], qkv, qkv[:, 2 * C:], 3 * C, o, go, C, lse, delta, dqkv[:, C:], dqkv, dqkv[:, 2 * C:],
                               3 * C, B, T, nh, hs, scale, drop_p=p_attn, rng_state=ctx.rng_state, rng_stream=sb)
-            side.append(lambda dqkv=dqkv, blk=blk, a=a: _dw_db(dqkv, a, blk["g_wqkv"], blk["g_bqkv"]))
+            side.append(lambda dqkv=dqkv, blk=blk, a=a: _dw_db(ctx, dqkv, a, blk["g_wqkv"], blk["g_bqkv"]))
             ga = bufs.get(nm + ".ga2", (M, C), adt)
             ops.linear_dx(dqkv, blk["wqkv16t"] if ctx.bf16 else blk["wqkv"], out=ga)
             g = blk["ln1"].bwd(ctx, ga, dres=g1, out=G[i - 1] if i > 0 else bufs.get(nm + ".g_tok", (M, C), sdt),
@@ -1102,15 +1125,18 @@ class VectorNet(object):
         R = B * L
         g_nchw = bufs.get(nm + ".g.nchw", (B, 64 * 64 * 64))
         ops.transpose(g_out.view(B, 4096, 64), g_nchw, B, 4096, 64)
-        ops.colsum(g_nchw, self.gen3.gb)
-        ops.linear_dw(g_nchw, gen_act, out=self.gen3.gw)
+        if not ctx.fz(self.gen3.gb):
+            ops.colsum(g_nchw, self.gen3.gb)
+        _dw(ctx, g_nchw, gen_act, self.gen3.gw)
         g_gen_act = ops.linear_dx(g_nchw, self.gen3.w, out=bufs.get(nm + ".g.gen_act", (B, 64)))
         g_gen_pre = self.gen_ln.bwd(ctx, g_gen_act)
-        ops.colsum(g_gen_pre, self.gen0.gb)
-        ops.linear_dw(g_gen_pre, fused, out=self.gen0.gw)
+        if not ctx.fz(self.gen0.gb):
+            ops.colsum(g_gen_pre, self.gen0.gb)
+        _dw(ctx, g_gen_pre, fused, self.gen0.gw)
         g_fused = ops.linear_dx(g_gen_pre, self.gen0.w, out=bufs.get(nm + ".g.fused", (B, 128)))
-        ops.colsum(g_fused, self.af3.gb)
-        ops.linear_dw(g_fused, af_act, out=self.af3.gw)
+        if not ctx.fz(self.af3.gb):
+            ops.colsum(g_fused, self.af3.gb)
+        _dw(ctx, g_fused, af_act, self.af3.gw)
         g_af_act = ops.linear_dx(g_fused, self.af3.w, out=bufs.get(nm + ".g.af_act", (B, 128)))
         g_af_pre = self.af_ln.bwd(ctx, g_af_act)
         # agent_fusion.0: columns 0:128 act on t0, columns 128:192 on the constant pe row
@@ -1124,20 +1150,21 @@ class VectorNet(object):
         ops.gemm(gsum, self.af0.w[:, 128:], g_pe, 1, 64, 128, 128, 192, 64, b_mode=ops.B_KN)
         # pos_emb branch (single row; its first Linear sees a zero input -> exactly-zero weight grad)
         ops.axpby(self.pe3.gb, g_pe.view(64), 1.0, 0.0)
-        ops.linear_dw(g_pe, pe_act, out=self.pe3.gw)
+        _dw(ctx, g_pe, pe_act, self.pe3.gw)
         g_pe_act = ops.linear_dx(g_pe, self.pe3.w, out=bufs.get(nm + ".g.pe_act", (1, 64)))
         g_pe_pre = self.pe_ln.bwd(ctx, g_pe_act)
         ops.axpby(self.pe0.gb, g_pe_pre.view(64), 1.0, 0.0)
         ops.fill(self.pe0.gw, 0.0)
         # to_out on lane 0 only
-        ops.colsum(g_t0, self.to_out.gb)
+        if not ctx.fz(self.to_out.gb):
+            ops.colsum(g_t0, self.to_out.gb)
         ops.gemm(g_t0, att0, self.to_out.gw, 128, 128, B, 128, 128, 128, a_mode=ops.A_COLMAJOR, b_mode=ops.B_KN)
         g_att0 = bufs.get(nm + ".g.att0", (B, 128))
         ops.gemm(g_t0, self.to_out.w, g_att0, B, 128, 128, 128, 128, 128, b_mode=ops.B_KN)
         dqkv = bufs.get(nm + ".g.qkv", (R, 384))
         hd = 128 // self.heads
         ops.lane0_attention_bwd(qkv, prob, g_att0, lane_num, B, L, self.heads, hd, hd ** -0.5, dqkv)
-        ops.linear_dw(dqkv, tok, out=self.qkv.gw)
+        _dw(ctx, dqkv, tok, self.qkv.gw)
         g = ops.linear_dx(dqkv, self.qkv.w, out=bufs.get(nm + ".g.tok", (R, 128)))
         for i in range(len(self.sub) - 1, -1, -1):
             lin, ln = self.sub[i]
@@ -1145,8 +1172,9 @@ class VectorNet(object):
             last = i == len(self.sub) - 1
             gy = ops.polyline_pool_bwd(g, arg, bufs.get("%s.g.sub%d.y" % (nm, i), (R * V, 64)), R, V, 64, last)
             g_pre = ln.bwd(ctx, gy)
-            ops.colsum(g_pre, lin.gb)
-            ops.linear_dw(g_pre, x_in, out=lin.gw)
+            if not ctx.fz(lin.gb):
+                ops.colsum(g_pre, lin.gb)
+            _dw(ctx, g_pre, x_in, lin.gw)
             if i > 0:
                 g = ops.linear_dx(g_pre, lin.w, out=bufs.get("%s.g.sub%d.x" % (nm, i), (R * V, 128)))
 
@@ -1231,14 +1259,16 @@ class RadarGAT(object):
         g_m2 = ops.log_softmax_bwd(g_out, out, bufs.get(nm + ".g.m2", (B * 256, 128)), B * 64, 512, True)
         if p > 0.0:
             ops.dropout_apply(g_m2, g_m2, p, ctx.rng_state, self.stream_base + 6)
-        ops.colsum(g_m2, self.m2.gb)
-        ops.linear_dw(g_m2, m1t, out=self.m2.gw)
+        if not ctx.fz(self.m2.gb):
+            ops.colsum(g_m2, self.m2.gb)
+        _dw(ctx, g_m2, m1t, self.m2.gw)
         g_m1t = ops.linear_dx(g_m2, self.m2.w, out=bufs.get(nm + ".g.m1t", m1t.shape))
         g_m1 = ops.transpose(g_m1t, bufs.get(nm + ".g.m1", (n_cat, 256)), B, 256, self.nh * N)
         if p > 0.0:
             ops.dropout_apply(g_m1, g_m1, p, ctx.rng_state, self.stream_base + 5)
-        ops.colsum(g_m1, self.m1.gb)
-        ops.linear_dw(g_m1, y2.view(n_cat, H2), out=self.m1.gw)
+        if not ctx.fz(self.m1.gb):
+            ops.colsum(g_m1, self.m1.gb)
+        _dw(ctx, g_m1, y2.view(n_cat, H2), self.m1.gw)
         g_y2 = ops.linear_dx(g_m1, self.m1.w, out=bufs.get(nm + ".g.y2", (n_cat, H2)))
         g_y1d = ops.elu_bwd(g_y2, y2, bufs.get(nm + ".g.y1d", (n_cat, H2)))
         if p > 0.0:
@@ -1313,15 +1343,17 @@ class Head(object):
         o = 0
         for gbuf in self.grads:
             n = gbuf.numel()
-            ops.axpby(gbuf, tot[o:o + n], 1.0, 0.0)
+            if not ctx.fz(gbuf):
+                ops.axpby(gbuf, tot[o:o + n], 1.0, 0.0)
             o += n
         # z0 = relu(join.4(.)): mask the GRU's gradient, then walk the MLP back; each dX GEMM applies
         # the ReLU mask of the layer below in its epilogue
         g = ops.relu_mask(dz, self.xs[-1], out=bufs.get("head.gz", dz.shape))
         for i in range(len(self.join) - 1, -1, -1):
             lin, x = self.join[i], self.xs[i]
-            ops.colsum(g, lin.gb)
-            ops.linear_dw(g, x, out=lin.gw)
+            if not ctx.fz(lin.gb):
+                ops.colsum(g, lin.gb)
+            _dw(ctx, g, x, lin.gw)
             gx = bufs.get("head.gx%d" % i, x.shape)
             if i > 0:
                 g = ops.linear_dx(g, lin.w, out=gx, aux=x, ldaux=x.shape[1])
@@ -1437,8 +1469,139 @@ class Engine(object):
         self.nonfinite_guard = False   # set_nonfinite_guard: skip an optimizer step whose gradient norm is not finite
         self._guard = None          # its device flag, skip counter and BatchNorm shadows (allocated when first armed)
         self._stats_tab = None      # tensor_stats: the device table of the layout's tensors
+        # frozen parameters (requires_grad = False), see trainable_mask()
+        self._mask_flags = None     # the tuple of flags the state below was built for
+        self._mask_held = 0         # > 0 inside mask_held(): the flags were read at the entry of the running step
+        self.frozen = frozenset()   # frozen names of the trained range
+        self._fz = frozenset()      # data pointers of their gradient views (a packed k/q/v window: all three frozen)
+        self._plan = None           # which sub-backwards still run (None: everything, nothing is frozen)
+        self._fill_tabs = {}        # readiness group -> fill_ranges table of the frozen ranges a launch may still write
+        self._filled = set()        # ... and the groups zeroed so far in the running backward
+        self._mask_table = None     # (optimizer group table it was built from, effective table with 255 over frozen float4s)
+        self.never_stepped = None   # names frozen at every optimizer step so far (None: no step yet): FusedAdamW.state_dict
         self.n_lanes = int(os.environ.get("MMFN_BRANCH_LANES", "3"))
         self.offload_wgrad = True   # transformer weight / bias gradients on the side stream (worth 3.9 ms per step)
+
+    # ------------------------------------------------------------------ frozen parameters
+    def trainable_mask(self):
+        """The parameters' requires_grad flags (a tuple, named_parameters() order), read at the entry of every step, backward and
+        optimizer step, by the autograd bridge and at every capture and replay.  The flags are the only source: when they differ
+        from the last read, the state derived from them is rebuilt (_install_mask) - outside a capture, and not while micro-steps
+        are pending."""
+        if self._mask_held:   # read at the entry of the running step (mask_held): one read of all flags per step
+            return self._mask_flags
+        flags = self.layout.trainable_flags()
+        if flags != self._mask_flags:
+            self._install_mask(flags)
+        return flags
+
+    @contextlib.contextmanager
+    def mask_held(self):
+        """Read the flags once and hold them for the block: the entry points inside (backward, optimizer_step, a replay) then
+        use this read instead of one each.  train_step / accumulate_step and the trainer's step wrap themselves in it."""
+        flags = self.trainable_mask()
+        self._mask_held += 1
+        try:
+            yield flags
+        finally:
+            self._mask_held -= 1
+
+    def fz(self, *grads):
+        """True when every one of these gradient views belongs to a frozen parameter."""
+        f = self._fz
+        if not f:
+            return False
+        for g in grads:
+            if g.data_ptr() not in f:
+                return False
+        return True
+
+    def _install_mask(self, flags):
+        L = self.layout
+        frozen = L.frozen_names(flags)
+        if frozen == self.frozen:   # (the first read with nothing frozen, or only never-trained tail tensors changed)
+            self._mask_flags = flags
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("requires_grad flags changed inside a hipGraph capture")
+        if self.accum_pending:
+            raise RuntimeError("requires_grad flags changed while %d accumulated micro-step(s) are pending: finish them with "
+                               "train_step() or drop them with discard_accumulated() first" % self.accum_pending)
+        self._mask_flags, self.frozen = flags, frozen
+        L.frozen = frozen
+        self._mask_table = None
+        self._fill_tabs = {}
+        if not frozen:
+            self._fz, self._plan = frozenset(), None
+            return
+        # gradient views by pointer; the packed k / q / v windows start at key.*: frozen as a window only when all three are
+        ptrs = set()
+        for n in frozen:
+            if ".attn.key." in n and not all(n.replace(".key.", k) in frozen for k in (".query.", ".value.")):
+                continue
+            ptrs.add(L.g(n).data_ptr())
+        self._fz = frozenset(ptrs)
+        live = [n for n in L.offsets if n not in L.unused and n not in frozen]
+        has = lambda *keys: any(all(k in n for k in keys) for n in live)
+        trunk_keys = ("image_encoder.", "lidar_encoder.", "img_map_encoder.")
+        layer = [[has(t, ".layer%d." % li) for li in range(5)] for t in trunk_keys]           # [m][li], li 1..4
+        first = [any(t in n and ".layer" not in n for n in live) or layer[m][1] for m, t in enumerate(trunk_keys)]   # stem + layer1
+        vec, rad = has("vectornet_encoder."), has("radar_encoder.")
+        if self.variant != "img":
+            first[2] = vec
+        gpt = [has("transformer%d." % (i + 1)) for i in range(4)]
+        act, below = [], False    # act[s]: something trainable in transformer s+1 or anywhere below it in the backward
+        for s in range(4):
+            below = below or gpt[s] or (s == 3 and rad) or any(first[m] if s == 0 else layer[m][s + 1] for m in range(3))
+            act.append(below)
+        self._plan = {"gpt": act, "rad": rad, "tail": first,
+                      "layer": [[s > 0 and (act[s - 1] or layer[m][s + 1]) for m in range(3)] for s in range(4)]}
+        # frozen ranges inside a sub-backward that this plan skips as a whole are written by no launch any more: zeroed once, here.
+        # Every other frozen range is zeroed once per backward, per readiness group, in front of the group's hook (_ready):
+        # byproducts of launches that run unchanged (BatchNorm / LayerNorm sums, one of a packed window, ...) and, deliberately,
+        # also the ranges whose single launch is pruned (ctx.fz) - which launch writes which tensor is known only where the
+        # launch is issued, and a second list of it here could go stale without any test noticing
+        skipped = []
+        for s in range(4):
+            if not act[s]:
+                skipped.append(("transformer%d." % (s + 1),))
+            for m, t in enumerate(trunk_keys):
+                if s > 0 and not self._plan["layer"][s][m]:
+                    skipped.append((t, ".layer%d." % (s + 1)))
+        for m, t in enumerate(trunk_keys):
+            if not first[m] and not (m == 2 and self.variant != "img"):
+                skipped += [(t, ".layer1."), (t, "stem")]
+        if self.vec is not None and not vec:
+            skipped.append(("vectornet_encoder.",))
+        if self.rad is not None and not rad:
+            skipped.append(("radar_encoder.",))
+
+        def clean(n):
+            for keys in skipped:
+                if keys[-1] == "stem":
+                    if keys[0] in n and ".layer" not in n:
+                        return True
+                elif all(k in n for k in keys):
+                    return True
+            return False
+
+        dirty = {}
+        for n in frozen:
+            if not clean(n):
+                dirty.setdefault((L.stage_of(n), L.GROUPS[L.group_of(n)]), []).append(n)
+        self._fill_tabs = {key: ops.fill_ranges_table(L.merged_ranges(names), self.device) for key, names in dirty.items()}
+        ops.fill_ranges(L.grads, ops.fill_ranges_table(L.merged_ranges(frozen), self.device))
+
+    def _group_table(self, n_groups):
+        """The AdamW launch's group table while something is frozen: 255 over frozen float4s, elsewhere what the unmasked launch
+        reads - the optimizer's ids when the step has several hyper rows, zeros when it has one (a step with one row runs
+        everything as group 0 whatever table an optimizer installed earlier)."""
+        ids = self.opt_group_of if n_groups > 1 else None
+        if self._mask_table is None or self._mask_table[0] is not ids:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the optimizer's group table changed inside a hipGraph capture")
+            self._mask_table = (ids, self.layout.group_table(self.frozen, ids).to(self.device))
+        return self._mask_table[1]
 
     # ------------------------------------------------------------------ LayerNorm folded into the Linear behind it (fp32 path)
     def ln_fold_now(self, training):
@@ -1684,7 +1847,10 @@ class Engine(object):
         has been written, so a data-parallel wrapper can start reducing that bucket.
         on_ready((stage, group)) is the finer hook: called - ON THE STREAM THAT WROTE THEM, which inside the branch lanes is a
         side stream - as soon as the gradients of one readiness group of a stage (params.FlatLayout.group_ranges: "head",
-        "gpt", "vec", "img", "lid", "map") are complete."""
+        "gpt", "vec", "img", "lid", "map") are complete.  With frozen parameters the hooks fire as always, in the same order; a
+        sub-backward nothing trainable needs is not issued (_install_mask) and the frozen ranges of a group hold +0.0 when its
+        hook fires."""
+        self.trainable_mask()
         self.backward_begin(dpred, gscale, on_ready=on_ready)
         for s in range(3, -1, -1):
             self.backward_scale(s, on_ready=on_ready)
@@ -1692,8 +1858,15 @@ class Engine(object):
                 on_stage(3 - s)
 
     def _ready(self, hook, stage, group):
-        if hook is not None and (stage, group) in self.layout.group_ranges:
-            hook((stage, group))
+        key = (stage, group)
+        tab = self._fill_tabs.get(key)
+        if tab is not None and key not in self._filled:
+            # gradients of frozen tensors that launches of this group wrote as a byproduct: back to +0.0, on the stream that
+            # wrote them, before anything reads the group
+            ops.fill_ranges(self.layout.grads, tab)
+            self._filled.add(key)
+        if hook is not None and key in self.layout.group_ranges:
+            hook(key)
 
     @_in_precision
     def backward_begin(self, dpred=None, gscale=None, on_ready=None):
@@ -1701,6 +1874,7 @@ class Engine(object):
         ctx, B = self._last
         bufs = ctx.bufs
         self._adj_done = False
+        self._filled = set()
         g_fused = self.head.bwd(ctx, dpred, gscale)
         if self.rad is None:   # (rad: the "head" group also holds the radar encoder, complete after the deepest transformer)
             self._ready(on_ready, 0, "head")
@@ -1720,6 +1894,17 @@ class Engine(object):
         G = self._G
         gpt = self.gpts[s]
         frames, base = self.frames + [1], self.group_base + [sum(self.frames)]
+        plan = self._plan
+        if plan is not None and not plan["gpt"][s]:
+            # nothing trainable in this transformer or anywhere below it: no launch, the groups are reported as always
+            self._ready(on_ready, st, "gpt")
+            if s == 3 and self.rad is not None:
+                self._ready(on_ready, 0, "head")
+            group = lambda m: "vec" if (s == 0 and m == 2 and self.variant != "img") else names[m]
+            self._branches([lambda m=m: self._ready(on_ready, st, group(m)) for m in range(3)])   # (the lanes' own order and streams)
+            if s == 0:
+                self._fill_rest()
+            return
         gtok = bufs.get("gtok%d" % s, (B, gpt.T, gpt.C), ctx.adt)
         for m, g in enumerate(G):
             if not (self._adj_done and m < 3):   # the three branch lanes of the previous scale already spread their gradient
@@ -1727,45 +1912,63 @@ class Engine(object):
         gin = gpt.bwd(ctx, gtok)
         self._ready(on_ready, st, "gpt")
         if s == 3 and self.rad is not None:
-            dF3 = ops.pool_bcast_add(G[3], gin, bufs.get("dF3.3", G[3].shape, G[3].dtype), base[3], 1)
-            self.rad.bwd(ctx, dF3)
+            if plan is None or plan["rad"]:
+                dF3 = ops.pool_bcast_add(G[3], gin, bufs.get("dF3.3", G[3].shape, G[3].dtype), base[3], 1)
+                self.rad.bwd(ctx, dF3)
             self._ready(on_ready, 0, "head")
         if s > 0:
             nxt = self.gpts[s - 1]
             gtok_next = bufs.get("gtok%d" % (s - 1), (B, nxt.T, nxt.C), ctx.adt)
 
             def stage(m):
+                if plan is not None and not plan["layer"][s][m]:   # this stage of the trunk and everything below it is frozen
+                    self._ready(on_ready, st, names[m])
+                    return None
                 d = ops.pool_bcast_add(G[m], gin, bufs.get("dF%d.%d" % (s, m), G[m].shape, G[m].dtype), base[m], frames[m])
                 g = trunks[m].layer_bwd(ctx, s + 1, d)
                 self._ready(on_ready, st, names[m])
                 # the adjoint of the next scale's upsample-add for this branch (its own 64 token rows of gtok) at the tail of
                 # the lane, beside the other lanes, instead of three launches on the main stream ahead of the transformer
-                ops.upsample_adj(g, gtok_next, base[m], frames[m])
+                if plan is None or plan["gpt"][s - 1]:
+                    ops.upsample_adj(g, gtok_next, base[m], frames[m])
                 return g
 
             self._G = self._branches([lambda m=m: stage(m) for m in range(3)])
             self._adj_done = True
             return
 
+        tail = (True, True, True) if plan is None else plan["tail"]   # False: the stem, layer1 (or VectorNet) are all frozen
+
         def img_tail():
-            d = ops.pool_bcast_add(G[0], gin, bufs.get("dF0.0", G[0].shape, G[0].dtype), base[0], frames[0])
-            self.img.stem_bwd(ctx, self.img.layer_bwd(ctx, 1, d))
+            if tail[0]:
+                d = ops.pool_bcast_add(G[0], gin, bufs.get("dF0.0", G[0].shape, G[0].dtype), base[0], frames[0])
+                self.img.stem_bwd(ctx, self.img.layer_bwd(ctx, 1, d))
             self._ready(on_ready, st, "img")
 
         def lid_tail():
-            d = ops.pool_bcast_add(G[1], gin, bufs.get("dF0.1", G[1].shape, G[1].dtype), base[1], frames[1])
-            self.lid.stem_bwd(ctx, self.lid.layer_bwd(ctx, 1, d))
+            if tail[1]:
+                d = ops.pool_bcast_add(G[1], gin, bufs.get("dF0.1", G[1].shape, G[1].dtype), base[1], frames[1])
+                self.lid.stem_bwd(ctx, self.lid.layer_bwd(ctx, 1, d))
             self._ready(on_ready, st, "lid")
 
         def map_tail():
-            d = ops.pool_bcast_add(G[2], gin, bufs.get("dF0.2", G[2].shape, G[2].dtype), base[2], frames[2])
-            if self.variant == "img":
-                self.map.stem_bwd(ctx, self.map.layer_bwd(ctx, 1, d))
-            else:
-                self.vec.bwd(ctx, d)
+            if tail[2]:
+                d = ops.pool_bcast_add(G[2], gin, bufs.get("dF0.2", G[2].shape, G[2].dtype), base[2], frames[2])
+                if self.variant == "img":
+                    self.map.stem_bwd(ctx, self.map.layer_bwd(ctx, 1, d))
+                else:
+                    self.vec.bwd(ctx, d)
             self._ready(on_ready, st, "map" if self.variant == "img" else "vec")
 
         self._branches([img_tail, lid_tail, map_tail])
+        self._fill_rest()
+
+    def _fill_rest(self):
+        """After the last scale: the frozen ranges of a group the backward did not report (none in the variants as built)."""
+        for key, tab in self._fill_tabs.items():
+            if key not in self._filled:
+                ops.fill_ranges(self.layout.grads, tab)
+                self._filled.add(key)
 
     # ------------------------------------------------------------------ optimizer
     def set_param_groups(self, group_of):
@@ -1814,6 +2017,7 @@ class Engine(object):
         if self.accum_pending:
             raise RuntimeError("%d accumulated micro-step(s) are pending: finish them with train_step() or drop them with "
                                "discard_accumulated() before a direct optimizer_step()" % self.accum_pending)
+        self.trainable_mask()
         groups = self.hyper_rows(lr, betas, eps, weight_decay, grad_scale, groups)
         self.set_hyper(groups)
         self.module.weights_changed()
@@ -1840,8 +2044,14 @@ class Engine(object):
         the non-finite guard's flag, every one of them behind it."""
         L, a = self.layout, self.average
         avg = None if a is None else (a.module._layout.params, a.n_averaged, a.ema_weight, a.mode_code)
-        ops.adamw_groups(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self.step_count, self.opt_hyper, n_groups,
-                         group_of=self.opt_group_of if n_groups > 1 else None, n=L.tail, coef=coef, avg=avg, ok=ok)
+        if self.frozen:
+            # the masked instance: frozen float4s keep parameter, moments and decay untouched (the average still follows them)
+            ops.adamw_groups(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self.step_count, self.opt_hyper, n_groups,
+                             group_of=self._group_table(n_groups), n=L.tail, coef=coef, avg=avg, ok=ok, mask=True)
+        else:
+            ops.adamw_groups(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self.step_count, self.opt_hyper, n_groups,
+                             group_of=self.opt_group_of if n_groups > 1 else None, n=L.tail, coef=coef, avg=avg, ok=ok)
+        self.never_stepped = self.frozen if self.never_stepped is None else (self.never_stepped & self.frozen)
         if a is not None:
             a.update_buffers(self.module, ok=ok)
             ops.step_advance(a.n_averaged, ok=ok)
@@ -1914,6 +2124,11 @@ class Engine(object):
         self.optimizer_step(lr=lr, grad_scale=1.0 / dp.world, **adam)
 
     def train_step(self, inp, gt, lr=1e-4, dp=None, clip_grad_norm=None, **adam):
+        """One training step (see _train_step) under a single read of the requires_grad flags."""
+        with self.mask_held():
+            return self._train_step(inp, gt, lr, dp, clip_grad_norm, **adam)
+
+    def _train_step(self, inp, gt, lr, dp, clip_grad_norm, **adam):
         """zero-grad (implicit: every gradient is overwritten) + forward + L1 + backward + AdamW
         (phase2_train_net.py:60-110).  `dp` (mmfn_amd.parallel.DataParallel) reduces the gradient
         buckets across ranks while the backward is still running.  `adam` may carry betas / eps /
@@ -1939,6 +2154,11 @@ class Engine(object):
 
     # ------------------------------------------------------------------ gradient accumulation / global-norm clipping
     def accumulate_step(self, inp, gt):
+        """One accumulation micro-step (see _accumulate_step) under a single read of the requires_grad flags."""
+        with self.mask_held():
+            return self._accumulate_step(inp, gt)
+
+    def _accumulate_step(self, inp, gt):
         """One micro-step of gradient accumulation: RNG advance, forward (BatchNorm running statistics update, as in the torch
         loop), L1 loss, backward, and acc += gradient per readiness group on the stream that wrote it.  No collective, no AdamW:
         the next train_step() folds the sum in.  Returns the device loss."""
@@ -1998,8 +2218,9 @@ class Engine(object):
                 slots[key] = (off, n)
                 off += n
             full = ops.grad_accum_blocks(L.tail)
-            self._norm = {"partials": torch.zeros(off + full, dtype=torch.float64, device=self.device), "groups": slots,
-                          "n_group_slots": off, "full": (off, full), "out": torch.zeros(2, dtype=torch.float32, device=self.device)}
+            # (one spare slot behind each range: the guard's look at the BatchNorm statistics while parameters are frozen, final_adam)
+            self._norm = {"partials": torch.zeros(off + 1 + full + 1, dtype=torch.float64, device=self.device), "groups": slots,
+                          "n_group_slots": off, "full": (off + 1, full), "out": torch.zeros(2, dtype=torch.float32, device=self.device)}
         return self._norm
 
     def group_hooks(self, mode, partials, user=None):
@@ -2077,7 +2298,17 @@ class Engine(object):
                 part = nm["partials"][o:o + n]
                 ops.grad_accum(L.grads[:L.tail], None, ops.ACCUM_NONE, part)
             else:
-                part = nm["partials"][:nm["n_group_slots"]]
+                o, n = 0, nm["n_group_slots"]
+                part = nm["partials"][:n]
+            if guard is not None and self.frozen and dp is None:
+                # Frozen parameters hide what the guard keys on: the backward of a frozen trunk is not run and a ReLU drops a
+                # NaN, so a non-finite input can leave every TRAINABLE gradient finite while the forward has already written
+                # non-finite BatchNorm running statistics.  One more partial - NaN when those statistics are not finite, else
+                # 0.0 (the norm keeps its bits) - makes the step skip and roll them back, as the same step does with nothing frozen.
+                # Single GPU only: the statistics are rank-local, and under data parallel every rank must reach the same
+                # decision from the reduced gradient alone
+                ops.nonfinite_slot(L.buffers_flat, nm["partials"][o + n:o + n + 1])
+                part = nm["partials"][o:o + n + 1]
             out = nm["out"]
             coef = out[1:2]
             ok, skipped = (None, None) if guard is None else (guard["ok"], guard["skipped"])

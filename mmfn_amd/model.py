@@ -49,6 +49,7 @@ class _AutogradBridge(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, anchor, module, inp):
+        module._engine_for().trainable_mask()
         pred, _ = module._engine_for().forward(inp, True, None)
         ctx.module = module
         return pred.clone()
@@ -61,7 +62,8 @@ class _AutogradBridge(torch.autograd.Function):
         # optimizer.zero_grad() / p.grad = None, phase2_train_net.py:60).  The explicit backward overwrites the flat gradient
         # buffer, so when the previous gradients are still attached they are parked and added back (two extra passes over the
         # buffer, on this path only; the fused Engine.train_step never accumulates)
-        held = next((p.grad for n, p in m.named_parameters() if n not in L.unused), None)
+        m._engine_for().trainable_mask()   # (first: a new mask zeroes the frozen ranges, before they are parked)
+        held = next((p.grad for n, p in m.named_parameters() if n not in L.unused and n not in L.frozen), None)
         accumulate = held is not None and held.data_ptr() >= L.grads.data_ptr() and \
             held.data_ptr() < L.grads.data_ptr() + L.grads.numel() * 4
         if accumulate:
@@ -69,7 +71,7 @@ class _AutogradBridge(torch.autograd.Function):
                 L.grads_parked = torch.empty_like(L.grads)
             L.grads_parked.copy_(L.grads)
         m._engine_for().backward(dpred.contiguous(), 1.0)
-        if accumulate:
+        if accumulate:   # (frozen ranges hold +0.0 on both sides: only the trainable ranges change)
             from . import ops
             ops.axpby(L.grads[:L.tail], L.grads_parked[:L.tail], 1.0, 1.0)
         L.attach_grads()
@@ -205,6 +207,34 @@ class MMFN(nn.Module):
         """(names, float64 [n, 3] device tensor of L2 norm, max |x| over the finite entries, non-finite count) per trained tensor of
         the last step's gradient ("grads") or of the parameters ("params"): engine.Engine.tensor_stats."""
         return self._engine_for().tensor_stats(which)
+
+    # ------------------------------------------------------------------ frozen parameters
+    def _set_trainable(self, prefixes, flag):
+        named = list(self.named_parameters())
+        hit = []
+        for pre in (prefixes or ("",)):
+            names = [n for n, _ in named if n.startswith(pre)]
+            if not names:
+                raise ValueError("no parameter name starts with %r" % (pre,))
+            hit += [n for n in names if n not in hit]
+        chosen = set(hit)
+        for n, p in named:
+            if n in chosen:
+                p.requires_grad_(flag)
+        return hit
+
+    def freeze(self, *prefixes):
+        """requires_grad_(False) on every parameter whose name starts with one of `prefixes` (none: all of them).  The fused step
+        then leaves them, their moments and their weight decay alone and prunes the backward work only they needed
+        (engine.Engine.trainable_mask).  Returns the names; a prefix that matches nothing is a ValueError."""
+        return self._set_trainable(prefixes, False)
+
+    def unfreeze(self, *prefixes):
+        """The inverse of freeze()."""
+        return self._set_trainable(prefixes, True)
+
+    def trainable_names(self):
+        return [n for n, p in self.named_parameters() if p.requires_grad]
 
     # ------------------------------------------------------------------ PID (model_vec.py:684-726)
     def control_pid(self, waypoints, velocity):

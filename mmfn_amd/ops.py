@@ -652,9 +652,11 @@ def conv2d_wgrad_winograd(dy, x, out, v=None):
 
 
 def _wgrad_winograd_body(dy, x, out, v, B, H, W, Ci, Co, T, dU, V, dMt, st, bn=None):
-    if v is not None:
+    """out None (conv2d_bwd_winograd with a frozen filter): only the transformed output gradient, which the data gradient shares."""
+    want_dw = out is not None
+    if want_dw and v is not None:
         V = v.view(-1)[:36 * T * Ci]
-    else:
+    elif want_dw:
         _call("mmfn_wino_input_f32", ptr(x), ptr(V), B, H, W, Ci, 4, st)
     if bn is not None:
         g, ymask, co, mean, rstd, weight, relu_bias, means, ge_out = bn
@@ -662,6 +664,8 @@ def _wgrad_winograd_body(dy, x, out, v, B, H, W, Ci, Co, T, dU, V, dMt, st, bn=N
               ptr(ge_out), ptr(dMt), B, H, W, Co, st)
     else:
         _call("mmfn_wino_outgrad_f32", ptr(dy), ptr(dMt), B, H, W, Co, st)
+    if not want_dw:
+        return None
     # the split-K combine of this GEMM (K = tiles: thousands) runs inside the output transform, which sums the slices as it reads
     info = {} if (WGRAD_SLABS and Ci % 64 == 0) else None
     gemm(dMt, V, dU, Co, Ci, T, Co, Ci, Ci, A_COLMAJOR, B_KN, batch=36, strideA=T * Co, strideB=T * Ci, strideC=Co * Ci, slab_info=info)
@@ -690,7 +694,7 @@ def conv2d_bwd_winograd(dy, x, u, dw_out, dx_out, v=None, res=None, bn=None):
     bn = (g, ymask or None, conv_out, mean, rstd, weight, relu_bias or None, means, ge_out or None), all NHWC / [C]: dy is then the
     BatchNorm backward of g (reductions already done by bn_bwd_reduce) formed on the fly inside the transform; the `dy` argument
     only gives the shape.  relu_bias (with ymask None): the ReLU mask is recomputed from conv_out (bn_bwd).
-    x: the convolution's input, or - with v given - anything carrying its .shape."""
+    x: the convolution's input, or - with v given - anything carrying its .shape.  dw_out None: no weight gradient (a frozen filter)."""
     B, H, W, Ci = x.shape
     Co = dy.shape[3]
     T = B * (H // 4) * (W // 4)
@@ -1164,21 +1168,27 @@ def weight_average(avg, src, n_averaged, ema_weight, mode, ok=None):
     _call("mmfn_weight_average_f32", ptr(avg), ptr(src), avg.numel(), ptr(n_averaged), ptr(ema_weight), int(mode), stream())
 
 
-ADAMW_COEF, ADAMW_AVG, ADAMW_GUARD = 1, 2, 4   # mirror include/mmfn_hip.h
+ADAMW_COEF, ADAMW_AVG, ADAMW_GUARD, ADAMW_MASK = 1, 2, 4, 8   # mirror include/mmfn_hip.h
+ADAMW_FROZEN = 255   # group_of byte of a float4 that belongs to a frozen parameter (ADAMW_MASK)
 
 
-def adamw_groups(p, g, m, v, step, hyper, n_groups, group_of=None, n=None, coef=None, avg=None, ok=None):
+def adamw_groups(p, g, m, v, step, hyper, n_groups, group_of=None, n=None, coef=None, avg=None, ok=None, mask=False):
     """AdamW with the hyper-parameter rows (and optional per-float4 group ids) in device memory.  coef: a device scalar that
     multiplies every group's grad_scale (the clip coefficient).  avg: (avg, n_averaged, ema_weight, mode), every new parameter is
     also folded into avg[0, n) as weight_average does.  ok (with coef): the non-finite guard's device flag (int32), the launch
-    touches nothing when it is 0."""
+    touches nothing when it is 0.  mask: float4s whose group_of byte is ADAMW_FROZEN keep p / m / v untouched (an average is still
+    updated from p); group_of is then mandatory, also with one group."""
     n = p.numel() if n is None else n
+    if mask and (group_of is None or group_of.dtype != torch.uint8 or group_of.numel() * 4 < n):
+        raise ValueError("the masked AdamW launch needs a uint8 group table with one byte per float4 of the range")
     a, n_averaged, ema_weight, mode = (None, None, None, 0) if avg is None else avg
     if a is not None and a.numel() < n:
         raise ValueError("average holds %d floats, the step covers %d" % (a.numel(), n))
     if ok is not None and coef is None:
         raise ValueError("the guarded AdamW launch is the coefficient instance: pass coef")
     variant = sum(bit for bit, arg in ((ADAMW_COEF, coef), (ADAMW_AVG, avg), (ADAMW_GUARD, ok)) if arg is not None)
+    if mask:
+        variant |= ADAMW_MASK
     _call("mmfn_adamw_groups_f32", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(group_of), ptr(hyper), n_groups, ptr(step), variant,
           ptr(coef), ptr(a), ptr(n_averaged), ptr(ema_weight), int(mode), ptr(ok), stream())
 
@@ -1231,6 +1241,30 @@ def tensor_stats_table(ranges, device):
     if not rows:
         raise ValueError("tensor_stats needs at least one range")
     return {"table": torch.tensor(rows, dtype=torch.int64).to(device), "n_chunks": first, "limit": limit}
+
+
+def fill_ranges_table(ranges, device):
+    """The device table of fill_ranges for [(offset, count), ...], offsets and counts multiples of 4 floats, no overlap:
+    tensor_stats_table's format."""
+    ranges = sorted(ranges)
+    for (off, n), nxt in zip(ranges, ranges[1:] + [None]):
+        if n % 4 or (nxt is not None and off + n > nxt[0]):
+            raise ValueError("fill_ranges ranges are whole float4s that do not overlap, got (%d, %d)" % (off, n))
+    return tensor_stats_table(ranges, device)
+
+
+def fill_ranges(flat, tab, value=0.0):
+    """flat[offset:offset + count] = value over every range of `tab` (fill_ranges_table) in one launch."""
+    if flat.dtype != torch.float32 or flat.numel() < tab["limit"] or not flat.is_contiguous():
+        raise ValueError("the table covers %d floats, the buffer holds %d %s" % (tab["limit"], flat.numel(), flat.dtype))
+    _call("mmfn_fill_ranges_f32", ptr(flat), ptr(tab["table"]), tab["table"].shape[0], tab["n_chunks"], float(value), stream())
+
+
+def nonfinite_slot(x, slot):
+    """slot (a one-element float64 view) = NaN when any entry of the fp32 tensor x is not finite, else 0.0."""
+    if x.dtype != torch.float32 or slot.dtype != torch.float64 or slot.numel() != 1 or not x.is_contiguous():
+        raise ValueError("nonfinite_slot takes a contiguous fp32 tensor and one float64 slot")
+    _call("mmfn_nonfinite_slot_f32", ptr(x), x.numel(), ptr(slot), stream())
 
 
 def tensor_stats(flat, tab, scale=1.0):

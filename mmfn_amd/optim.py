@@ -70,12 +70,29 @@ class FusedAdamW(object):
                 seen.add(n)
                 names.append(n)
             self._group_names.append(names)
-        missing = set(by_id.values()) - seen
-        if missing:
-            raise ValueError("param_groups must cover every parameter of the model (missing e.g. %s)" % sorted(missing)[:3])
+        # parameters in no group: allowed while they are frozen - optim.AdamW(filter(lambda p: p.requires_grad, ...)) - and
+        # checked again at every step (a parameter unfrozen later has no hyper-parameters to step with)
+        self._ungrouped = {n: p for n, p in model.named_parameters() if n not in seen}
+        self._check_ungrouped()
         if len(self.param_groups) > 16:
             raise ValueError("at most 16 parameter groups")
         self._install_groups()
+
+    def _check_ungrouped(self):
+        missing = [n for n, p in self._ungrouped.items() if p.requires_grad]
+        if missing:
+            raise ValueError("param_groups must cover every parameter of the model (missing e.g. %s)" % sorted(missing)[:3])
+
+    def group_table(self):
+        """The effective group table of the AdamW launch (params.FlatLayout.group_table): the group ids with 255 over the float4s
+        of the frozen parameters.  Built on the host; the engine builds the same on the device when something is frozen."""
+        L = self.model._layout
+        gid = torch.zeros(L.total // 4, dtype=torch.uint8)
+        for gi, names in enumerate(self._group_names):
+            for n in names:
+                b, e = L.span(n)
+                gid[b // 4:e // 4] = gi
+        return L.group_table(L.frozen_names(), gid)
 
     def _install_groups(self):
         """One group id per float4 of the flat buffer (tensors are 16-byte aligned in it), handed to the engine."""
@@ -98,6 +115,7 @@ class FusedAdamW(object):
 
     def hyper_rows(self):
         """[(lr, beta1, beta2, eps, weight_decay)] per group - what Engine.optimizer_step(groups=...) takes."""
+        self._check_ungrouped()
         return [(g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"]) for g in self.param_groups]
 
     def zero_grad(self, set_to_none=True):
@@ -105,7 +123,8 @@ class FusedAdamW(object):
             p.grad = None  # the flat gradient buffer is overwritten, never accumulated, by every backward
 
     def step(self, grad_scale=1.0):
-        self.model._engine_for().optimizer_step(grad_scale=grad_scale, groups=self.hyper_rows())
+        rows = self.hyper_rows()   # (first: a parameter unfrozen outside every group raises before anything is launched)
+        self.model._engine_for().optimizer_step(grad_scale=grad_scale, groups=rows)
 
     # ------------------------------------------------------------------ torch.optim.AdamW-format state
     def _moment_views(self):
@@ -130,9 +149,10 @@ class FusedAdamW(object):
         eng = self.model._engine_for()
         steps = int(eng.step_count.item())
         state = {}
+        never = eng.never_stepped or ()   # frozen at every optimizer step so far: torch holds no state for them either
         if steps > 0:
             for idx, (name, m, v) in enumerate(self._moment_views()):
-                if name in L.unused:
+                if name in L.unused or name in never:
                     continue
                 state[idx] = {"step": torch.tensor(float(steps)), "exp_avg": m.clone().contiguous(),
                               "exp_avg_sq": v.clone().contiguous()}
@@ -158,15 +178,18 @@ class FusedAdamW(object):
                 if k in theirs:
                     mine[k] = tuple(theirs[k]) if k == "betas" else theirs[k]
         steps = set()
+        absent = set()
         L.exp_avg.zero_()
         L.exp_avg_sq.zero_()
         for idx, (name, m, v) in enumerate(self._moment_views()):
             st = sd["state"].get(idx, sd["state"].get(str(idx)))
             if st is None:
+                absent.add(name)
                 continue
             m.copy_(st["exp_avg"])
             v.copy_(st["exp_avg_sq"])
             steps.add(int(float(st["step"])))
         if len(steps) > 1:
             raise ValueError("per-parameter step counts differ (%s): one shared counter is kept on the device" % sorted(steps))
+        eng.never_stepped = frozenset(absent) if steps else None
         eng.step_count.fill_(steps.pop() if steps else 0)

@@ -271,6 +271,9 @@ class GraphedStep(object):
     per-group fold (fold=True) in front of each bucket's reduction, optional clipping (clip_grad_norm), AdamW.  k, the size r of a
     partial group, max_norm and the learning rate only change the device hyper table (set in __call__), never the capture.
 
+    Frozen parameters (Engine.trainable_mask): the capture holds the backward pruned for the requires_grad flags of that moment and
+    the AdamW launch masked for them; a replay after the flags changed raises, like the checks below.
+
     Non-finite guard (Engine.set_nonfinite_guard): a "final" step captured while it is armed holds the guarded launches (the norm
     is always measured, max_norm = inf without clip_grad_norm) and replays only while it stays armed; the BatchNorm snapshot of
     a group's first micro-step is issued by __call__ in front of the replay, outside the capture.  The plain "step" variant has
@@ -291,6 +294,7 @@ class GraphedStep(object):
         self.lr, self.adam = lr, adam
         eng = engine
         self.guard = eng.nonfinite_guard   # the captured final_adam holds the guarded launches (or not): see __call__
+        self.mask = eng.trainable_mask()   # the pruned backward and the masked AdamW launch are captured for these flags
         if warm and variant != "step" and eng.accum_pending:
             raise RuntimeError("warm-up steps would consume the %d pending micro-steps: capture with warm=0" % eng.accum_pending)
         for _ in range(warm):  # size every buffer / scratch lane eagerly before capture
@@ -371,6 +375,8 @@ class GraphedStep(object):
 
         pending = eng.accum_pending
         self.average = eng.average   # folded into the captured AdamW launch (or not): a replay must find the same attachment
+        if eng.trainable_mask() != self.mask:
+            raise RuntimeError("requires_grad flags changed during the warm-up steps of a capture")
         try:
             rec.capture(body)
         finally:
@@ -390,6 +396,9 @@ class GraphedStep(object):
             raise RuntimeError("this step was captured %s; the engine now has %s: capture the step again" % (
                 "with an attached weight average" if self.average is not None else "without a weight average",
                 "a different one" if eng.average is not None else "none"))
+        if eng.trainable_mask() != self.mask:
+            raise RuntimeError("this step was captured with other requires_grad flags (%d parameter(s) differ): capture the step again"
+                               % sum(a != b for a, b in zip(eng._mask_flags, self.mask)))
         if self.variant != "micro" and eng.nonfinite_guard != self.guard:
             raise RuntimeError("this step was captured with the non-finite guard %s; the engine now has it %s: capture the step again"
                                % (("armed", "disarmed") if self.guard else ("disarmed", "armed")))

@@ -208,6 +208,7 @@ class FlatLayout(object):
             b, e = self.group_ranges.get(key, (o, o))
             self.group_ranges[key] = (min(b, o), max(e, o + (k + 3) // 4 * 4))
         self.unused = unused
+        self.frozen = frozenset()   # trained-range names whose requires_grad is False, as the engine last read them (Engine.trainable_mask)
         self.device = None
         self.params = self.grads = self.exp_avg = self.exp_avg_sq = None
         self.buffers_flat = None
@@ -350,10 +351,47 @@ class FlatLayout(object):
         return self.params[off:off + n].view(count_rows, cols), self.grads[off:off + n].view(count_rows, cols)
 
     def attach_grads(self):
-        """Expose the flat gradient buffer through p.grad (autograd-compatible training loops)."""
+        """Expose the flat gradient buffer through p.grad (autograd-compatible training loops); a frozen parameter keeps None."""
         named = dict(self.module.named_parameters())
         for name, gv in self.grad_views.items():
-            named[name].grad = None if name in self.unused else gv
+            named[name].grad = None if (name in self.unused or name in self.frozen) else gv
+
+    # ------------------------------------------------------------------ frozen parameters (requires_grad = False)
+    def trainable_flags(self):
+        """requires_grad of every parameter, in named_parameters() order."""
+        plist = self.__dict__.get("_plist")
+        if plist is None:
+            plist = self._plist = [p for _, p in self.module.named_parameters()]
+        return tuple(p.requires_grad for p in plist)
+
+    def frozen_names(self, flags=None):
+        """The names of the trained range whose flag is False."""
+        flags = self.trainable_flags() if flags is None else flags
+        return frozenset(n for n, f in zip(self.names, flags) if not f and n not in self.unused)
+
+    def span(self, name):
+        """[begin, end) of a tensor in floats, the end padded to the float4 the next tensor starts at."""
+        off, n = self.offsets[name]
+        return off, off + (n + 3) // 4 * 4
+
+    def merged_ranges(self, names):
+        """[(offset, count)] covering the named tensors, whole float4s, adjacent tensors merged into one range."""
+        out = []
+        for b, e in sorted(self.span(n) for n in names):
+            if out and out[-1][1] == b:
+                out[-1][1] = e
+            else:
+                out.append([b, e])
+        return [(b, e - b) for b, e in out]
+
+    def group_table(self, frozen, group_of=None):
+        """The optimizer's effective group table: one byte per float4 of the flat buffer, the optimizer's group id (group_of, a
+        uint8 tensor, or zeros) with 255 (MMFN_ADAMW_FROZEN) over the float4s of the frozen names.  A CPU uint8 tensor."""
+        gid = torch.zeros(self.total // 4, dtype=torch.uint8) if group_of is None else group_of.detach().to("cpu", copy=True)
+        for n in frozen:
+            b, e = self.span(n)
+            gid[b // 4:e // 4] = 255
+        return gid
 
 
 def default_unused(variant):

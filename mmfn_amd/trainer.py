@@ -156,26 +156,29 @@ class Trainer(object):
                 lr = optimizer.param_groups[0]["lr"]
                 inp = _bucket_lanes(inp, lane_bucket)  # in both modes, so that eager and replayed steps are bit-identical
                 if graph:
-                    sig = StaticBatchStep.signature(inp, gt)
-                    if average is not None:   # a capture with the average in its AdamW launch is a shape of its own
-                        sig = (sig, "average")
-                    state = self._static_steps.pop(sig, None)
-                    if state is None:  # first batch of this shape: eager (allocates the engine's buffers for it)
-                        state = "seen"
-                        loss = eng.train_step(inp, gt, lr=lr, dp=dp, **adam)
-                    else:
-                        if state == "seen":
-                            try:
-                                state = StaticBatchStep(eng, dp, inp, gt, lr, **adam)
-                            except RuntimeError as exc:  # a failed capture must not take the run down: this shape stays eager
-                                import warnings
-                                warnings.warn("hipGraph capture of the training step failed (%s); continuing with eager launches" % exc)
-                                torch.cuda.synchronize()
-                                state = "eager"
-                        loss = eng.train_step(inp, gt, lr=lr, dp=dp, **adam) if state == "eager" else state(inp, gt, lr=lr, **adam)
-                    self._static_steps[sig] = state  # re-inserted last: the dict is the LRU order
-                    while len(self._static_steps) > self.max_captured_shapes:
-                        _evict_lru(self._static_steps)
+                    with eng.mask_held() as mask:   # one read of the flags for the signature and the replay
+                        sig = StaticBatchStep.signature(inp, gt)
+                        if average is not None:   # a capture with the average in its AdamW launch is a shape of its own
+                            sig = (sig, "average")
+                        if eng.frozen:   # ... and so is one pruned and masked for frozen parameters, per set of flags
+                            sig = (sig, mask)
+                        state = self._static_steps.pop(sig, None)
+                        if state is None:  # first batch of this shape: eager (allocates the engine's buffers for it)
+                            state = "seen"
+                            loss = eng.train_step(inp, gt, lr=lr, dp=dp, **adam)
+                        else:
+                            if state == "seen":
+                                try:
+                                    state = StaticBatchStep(eng, dp, inp, gt, lr, **adam)
+                                except RuntimeError as exc:  # a failed capture must not take the run down: this shape stays eager
+                                    import warnings
+                                    warnings.warn("hipGraph capture of the training step failed (%s); continuing with eager launches" % exc)
+                                    torch.cuda.synchronize()
+                                    state = "eager"
+                            loss = eng.train_step(inp, gt, lr=lr, dp=dp, **adam) if state == "eager" else state(inp, gt, lr=lr, **adam)
+                        self._static_steps[sig] = state  # re-inserted last: the dict is the LRU order
+                        while len(self._static_steps) > self.max_captured_shapes:
+                            _evict_lru(self._static_steps)
                 else:
                     loss = eng.train_step(inp, gt, lr=lr, dp=dp, **adam)
             else:
@@ -235,6 +238,10 @@ class Trainer(object):
                            "(%s%s)" % (steps, len(bad), len(names), ", ".join(bad[:5]), ", ..." if len(bad) > 5 else ""))
 
     def _accum_call(self, eng, dp, inp, gt, lr, adam, final, fold, clip, graph, average=None):
+        with eng.mask_held() as mask:   # one read of the flags for the signature and the step
+            return self._accum_call_held(eng, dp, inp, gt, lr, adam, final, fold, clip, graph, average, mask)
+
+    def _accum_call_held(self, eng, dp, inp, gt, lr, adam, final, fold, clip, graph, average, mask):
         """One batch of an accumulation group: a micro-step, or (final) the step that closes the group.  graph=True: per
         (shape, variant) the first call runs eagerly, the second captures (parallel.StaticBatchStep), later ones replay."""
         if not graph:
@@ -245,6 +252,8 @@ class Trainer(object):
             sig = sig + ("average",)
         if eng.nonfinite_guard and final:   # (the guarded launches are a capture of their own; micro-steps have none)
             sig = sig + ("guard",)
+        if eng.frozen:   # (frozen parameters: the pruned backward and the masked AdamW are captures of their own, per set of flags)
+            sig = sig + (mask,)
         state = self._static_steps.pop(sig, None)
         if state is not None and state != "eager":
             if state == "seen":
