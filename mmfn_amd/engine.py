@@ -1191,6 +1191,10 @@ class RadarGAT(object):
     def __init__(self, name, layout, prefix, mod):
         self.name = name
         self.nh = mod.nheads
+        if self.nh > 3:
+            # head h draws its attention mask from stream_base + 1 + h; the sites after the heads use stream_base + 4, 5 and 6
+            raise ValueError("RadarGAT numbers its dropout streams 901 + head and 904..906 for the later sites: nheads = %d would "
+                             "give a head the mask stream of a later site (at most 3 heads)" % self.nh)
         self.alpha = mod.alpha
         self.p = mod.dropout
         self.W = [layout.w("%s.attention_%d.W" % (prefix, i)) for i in range(self.nh)]
