@@ -602,6 +602,45 @@ int mmfn_nchw_to_nhwc_f32(const float* in, float* out, int B, int C, int P, cons
 int mmfn_lidar_splat_f32(const float* pts, int B, int N, int stride_floats, float* out, int flip_y, void* stream);
 int mmfn_lane_to_vector_f32(const float* lane, float* vec, int64_t R, int n, void* stream);
 
+/* ---- batch assembly from a device-resident sample store (data.ResidentFrames / ResidentLoader) ----------------------------
+ * One launch gathers every field of a batch by sample index: what PackedFrames.batch, the host->device copy and the u8 -> f32
+ * widening of stage_batch do.  Values are moved unchanged (u8 widened exactly); destinations are f32.
+ *   dense  (row_off == NULL): dst[b * dst_stride + dst_offset + j] = f32(src[index[b] * row_elems + j]),  j < row_elems
+ *   ragged (row_off [n + 1], an ascending int64 prefix sum of rows per sample, DEVICE memory): the rows_b = row_off[i + 1] -
+ *          row_off[i] source rows of sample i = index[b], each row_elems long, land at dst[b * dst_stride + dst_offset ...];
+ *          the rows from rows_b up to lmax are written as +0.0 and count_out[b] = rows_b (int32; count_out may be NULL).
+ *          rows_b <= lmax is the caller's to guarantee (a larger set is cut at lmax rows).
+ * dst_stride / dst_offset (in floats) place frame s of a sample at batch entry b * S + s when a sample has S frames
+ * (dst_stride = S * row_elems, dst_offset = s * row_elems: model_vec.py:506-508).
+ * index: DEVICE int64 [B], read by the kernel - a captured launch follows the buffer's contents; entries outside [0, n) are
+ * clamped into it.  Any row length and any element alignment are accepted: 16-byte accesses wherever source and destination
+ * rows are misaligned alike, element accesses otherwise.
+ * MMFN_EINVAL: table or index NULL, index not 8-byte aligned, n_fields outside 1..MMFN_GATHER_MAX_FIELDS, a field's src or dst
+ * NULL or not aligned to its element, an unknown src_type, a negative size, B > 65535, n < 1 with work to do; nothing is
+ * launched then. */
+#define MMFN_GATHER_MAX_FIELDS 16
+#define MMFN_GATHER_U8 0
+#define MMFN_GATHER_F32 1
+typedef struct mmfn_gather_field {
+  const void* src;        /* dense: [n, row_elems]; ragged: the samples' rows concatenated, [row_off[n], row_elems] */
+  float* dst;
+  const int64_t* row_off; /* ragged only */
+  int32_t* count_out;     /* ragged only: [B] */
+  int64_t row_elems;      /* elements per source row */
+  int64_t dst_stride;     /* floats between the destinations of batch samples b and b + 1 */
+  int64_t dst_offset;     /* floats */
+  int32_t src_type;       /* MMFN_GATHER_U8 / MMFN_GATHER_F32 */
+  int32_t lmax;           /* ragged only: destination rows per sample */
+} mmfn_gather_field;
+typedef struct mmfn_gather_table {
+  mmfn_gather_field f[MMFN_GATHER_MAX_FIELDS];
+  int32_t n_fields;
+  int32_t reserved;
+} mmfn_gather_table;
+int mmfn_sizeof_gather_table(void);
+/* table: HOST memory, copied into the launch (by value); n = samples in the store */
+int mmfn_gather_batch(const mmfn_gather_table* table, const int64_t* index, int B, int64_t n, void* stream);
+
 /* ---- VectorNet polyline max-pool + concat (model_vec.py:269-282) -------------------------------- */
 /* Lane attention of VectorNet for QUERY 0 ONLY (model_vec.py:301-324 MaskSelfAttention, of which VectornetEncoder.forward
  * :412 consumes lane 0's row alone): any number of lanes, keys >= kv_len[b] masked as the reference's -1e9 fill, kv_len 0 =

@@ -77,6 +77,19 @@ class Conv16HaloDesc(ctypes.Structure):
                                                                 "stats_mode")]
 
 
+GATHER_MAX_FIELDS, GATHER_U8, GATHER_F32 = 16, 0, 1
+
+
+class GatherField(ctypes.Structure):
+    """mmfn_gather_field (include/mmfn_hip.h): one field of a batch gathered from a device-resident store."""
+    _fields_ = [("src", _vp), ("dst", _vp), ("row_off", _vp), ("count_out", _vp), ("row_elems", _i64), ("dst_stride", _i64),
+                ("dst_offset", _i64), ("src_type", _i32), ("lmax", _i32)]
+
+
+class GatherTable(ctypes.Structure):
+    _fields_ = [("f", GatherField * GATHER_MAX_FIELDS), ("n_fields", _i32), ("reserved", _i32)]
+
+
 G16_NT, G16_CONV_FWD, G16_CONV_DGRAD, G16_TN, G16_CONV_WGRAD = 0, 1, 2, 3, 4
 EPI16_OUT_F32 = 1024
 EPI16_RES_F32 = 2048
@@ -140,6 +153,8 @@ def lib():
             raise MMFNLibraryError("mmfn_conv16_halo_desc layout mismatch between C and ctypes")
         if handle.mmfn_sizeof_gpt_block_desc() != ctypes.sizeof(GptBlockDesc):
             raise MMFNLibraryError("mmfn_gpt_block_desc layout mismatch between C and ctypes")
+        if handle.mmfn_sizeof_gather_table() != ctypes.sizeof(GatherTable):
+            raise MMFNLibraryError("mmfn_gather_table layout mismatch between C and ctypes")
         _lib = handle
     return _lib
 

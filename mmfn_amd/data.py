@@ -12,7 +12,8 @@ cross PCIe as uint8 (the reference widens them to fp32 on the host first, 4x the
 float64 lane / radar / label tensors are narrowed to fp32 on the host before the copy.
 
 Host-side only (numpy / torch CPU tensors + async copies): no kernels live here, and nothing here is
-part of the CPU oracle.
+part of the CPU oracle - with one exception: ResidentFrames / ResidentLoader keep the packed store in HBM and
+assemble every batch with one launch of the gather kernel (csrc/resident.hip, through ops.gather_batch).
 """
 import os
 import pickle
@@ -284,6 +285,28 @@ _TORCH_DTYPE = {np.dtype(k).str: v for k, v in (("uint8", torch.uint8), ("int8",
                                                   ("float64", torch.float64), ("bool", torch.bool))}
 
 
+def _epoch_order(n, shuffle, sampler, seed, epoch):
+    """Sample order of one epoch, shared by PackedLoader and ResidentLoader: the sampler's, else a seeded permutation, else 0..n-1."""
+    if sampler is not None:
+        return [int(i) for i in sampler]
+    if shuffle:
+        g = torch.Generator()
+        g.manual_seed(seed + epoch)
+        return torch.randperm(n, generator=g).tolist()
+    return list(range(n))
+
+
+def _chunks(order, batch_size, drop_last):
+    chunks = [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
+    if drop_last and chunks and len(chunks[-1]) < batch_size:
+        chunks.pop()
+    return chunks
+
+
+def _num_batches(n, batch_size, drop_last):
+    return n // batch_size if drop_last else (n + batch_size - 1) // batch_size
+
+
 class PackedLoader(object):
     """Iterates collated batches of a PackedFrames store; a background thread assembles them `prefetch` batches ahead into
     pinned memory (the caching host allocator keeps a block until the asynchronous copy that reads it has completed).
@@ -296,28 +319,18 @@ class PackedLoader(object):
         self.epoch = 0
 
     def _order(self):
-        if self.sampler is not None:
-            return [int(i) for i in self.sampler]
-        n = len(self.packed)
-        if self.shuffle:
-            g = torch.Generator()
-            g.manual_seed(self.seed + self.epoch)
-            return torch.randperm(n, generator=g).tolist()
-        return list(range(n))
+        return _epoch_order(len(self.packed), self.shuffle, self.sampler, self.seed, self.epoch)
 
     def __len__(self):
         n = len(self.sampler) if self.sampler is not None else len(self.packed)
-        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+        return _num_batches(n, self.batch_size, self.drop_last)
 
     def __iter__(self):
         import queue
         import threading
         order = self._order()
         self.epoch += 1
-        B = self.batch_size
-        chunks = [order[i:i + B] for i in range(0, len(order), B)]
-        if self.drop_last and chunks and len(chunks[-1]) < B:
-            chunks.pop()
+        chunks = _chunks(order, self.batch_size, self.drop_last)
         q, stop = queue.Queue(maxsize=self.prefetch), threading.Event()
 
         def work():
@@ -347,6 +360,231 @@ class PackedLoader(object):
                     q.get_nowait()
                 except queue.Empty:
                     t.join(timeout=0.05)
+
+
+# ------------------------------------------------------------------------------------------ device-resident frames
+# PackedLoader still moves every batch host -> device (one np.take per field into pinned memory, a copy, a u8 -> f32 widening):
+# ~0.7-0.9 MB of host memcpy per sample on one Python thread per rank.  A 0.73 MB sample times 100 000 frames is 73 GB, and one
+# MI355X has 288 GB: ResidentFrames uploads the fields the engine reads ONCE, and ResidentLoader then assembles a batch with a single
+# gather launch by index (csrc/resident.hip) on the consumer's stream - no host thread, no pinned staging, no PCIe per batch.
+# Bit-identical to MMFN._pack(*stage_batch(PackedFrames.batch(idx))[0]) (tests/test_resident_gpu.py).
+RESIDENT_RESERVE_BYTES = 24 << 30   # kept free of the store by default: the engine's ~20 GB of buffers at batch 32, graph pools, slack
+_BOUNCE_BYTES = 32 << 20            # pinned upload buffer
+
+
+class ResidentFrames(object):
+    """A PackedFrames store (or the static shard `indices` of it) in device memory, reduced to what the `variant`'s engine input
+    reads: camera and LiDAR frames, target point, velocity, waypoints; lane sets (vec, rad) or raster maps (img); radar and
+    radar_adj (rad).  u8 stays u8 and f32 stays f32; float64 arrays and the JSON scalars are rounded to f32 on the host, the same
+    conversion stage_batch applies before its copy.  Resident row r holds sample indices[r]."""
+
+    def __init__(self, packed, device, config, variant, indices=None, max_bytes=None):
+        plan = self.plan(packed, config, variant, indices)
+        self.device = torch.device(device)
+        if max_bytes is None:
+            if self.device.type != "cuda":
+                raise ValueError("ResidentFrames keeps the store in GPU memory (got device %s)" % self.device)
+            max_bytes = torch.cuda.mem_get_info(self.device)[0] - RESIDENT_RESERVE_BYTES
+        if plan["bytes"] > max_bytes:
+            raise ValueError("ResidentFrames: the store needs %d bytes of device memory, %d are available (free memory less a "
+                             "%d-byte reserve for the engine's buffers unless max_bytes says otherwise); shard it with `indices` "
+                             "or stay with PackedLoader" % (plan["bytes"], max_bytes, RESIDENT_RESERVE_BYTES))
+        self.config, self.variant, self.plan_ = config, variant, plan
+        self.seq_len, self.pred_len = config.seq_len, config.pred_len
+        rows = plan["rows"]
+        self.n = len(rows)
+        self.indices = rows
+        self._row_of = np.full(len(packed), -1, dtype=np.int64)
+        self._row_of[rows] = np.arange(self.n, dtype=np.int64)     # (a repeated sample keeps its last row)
+        self.shapes = {nm: tuple(packed.arrays[nm].shape[1:]) for nm in plan["arrays"]}
+        self.tensors = {}
+        bounce = torch.empty(_BOUNCE_BYTES, dtype=torch.uint8, pin_memory=self.device.type == "cuda")
+        for nm in plan["arrays"]:
+            src = packed.arrays[nm]
+            if nm in packed.offsets:   # ragged: the kept samples' rows, concatenated in resident order
+                off = packed.offsets[nm]
+                counts = (off[1:] - off[:-1])[rows]
+                self.lane_counts = counts.astype(np.int64)
+                new_off = np.concatenate([[0], np.cumsum(self.lane_counts)]).astype(np.int64)
+                take = np.concatenate([np.arange(off[i], off[i + 1]) for i in rows]) if self.n else np.zeros(0, np.int64)
+                self.tensors[nm] = self._upload(src, take, bounce)
+                self.tensors[nm + ".row_off"] = torch.from_numpy(new_off).to(self.device)
+            else:
+                self.tensors[nm] = self._upload(src, rows, bounce)
+        f32 = lambda t: t.to(torch.float32).to(self.device)
+        for nm, t in self._labels(packed, config, rows).items():
+            self.tensors[nm] = f32(t)
+        del bounce
+
+    # ---- what goes to the device, and how many bytes: no device needed
+    @classmethod
+    def plan(cls, packed, config, variant, indices=None):
+        """{"fields": {name: bytes}, "bytes": total, "arrays": [packed array names], "rows": int64 sample ids}: the kept fields
+        and the exact device bytes of ResidentFrames(packed, ..., variant, indices), computed from the schema alone."""
+        if variant not in ("vec", "img", "rad"):
+            raise ValueError("variant must be 'vec', 'img' or 'rad', got %r" % (variant,))
+        S = config.seq_len
+        if variant != "img" and S > 1:
+            raise NotImplementedError("seq_len > 1 runs on the image-map model only (variant 'img')")
+        rows = np.arange(len(packed), dtype=np.int64) if indices is None else np.asarray(list(indices), dtype=np.int64)
+        if rows.size and (rows.min() < 0 or rows.max() >= len(packed)):
+            raise IndexError("sample index out of range")
+        n = len(rows)
+
+        def frames(key, count):
+            items = packed.fields[key]["items"] if packed.fields[key]["kind"] == "list" else [packed.fields[key]]
+            if len(items) < count:
+                raise ValueError("the store holds %d %s frame(s) per sample, the model reads %d" % (len(items), key, count))
+            return [it["name"] for it in items[:count]]
+
+        arrays = frames("fronts", S) + frames("lidars", S)
+        if variant == "img":
+            arrays += frames("maps", S)
+        else:
+            arrays += frames("vectormaps", 1)      # the lane set of frame 0 is the one MMFN._pack reads
+        if variant == "rad":
+            arrays += frames("radar", 1) + frames("radar_adj", 1)
+        fields = {}
+        for nm in arrays:
+            src = packed.arrays[nm]
+            if src.dtype not in (np.uint8, np.float32, np.float64):
+                raise ValueError("ResidentFrames: field %s has dtype %s (u8, f32 and f64 are supported)" % (nm, src.dtype))
+            esz = 1 if src.dtype == np.uint8 else 4
+            row = int(np.prod(src.shape[1:], dtype=np.int64))
+            if nm in packed.offsets:
+                off = packed.offsets[nm]
+                fields[nm] = int((off[1:] - off[:-1])[rows].sum()) * row * esz
+                fields[nm + ".row_off"] = (n + 1) * 8
+            else:
+                fields[nm] = n * row * esz
+        fields["target_point"] = n * 2 * 4
+        fields["velocity"] = n * 4
+        n_wp = len(packed.fields["waypoints"]["items"]) - S
+        fields["waypoints"] = n * n_wp * 2 * 4
+        if len(arrays) + 3 > 16:
+            raise ValueError("a batch of %d fields does not fit the 16 fields of one gather launch" % (len(arrays) + 3))
+        return {"fields": fields, "bytes": int(sum(fields.values())), "arrays": arrays, "rows": rows}
+
+    @staticmethod
+    def _labels(packed, config, rows):
+        """target_point [n, 2], velocity [n] and gt [n, pred_len, 2] with the expressions of stage_batch, before its f32 rounding."""
+        data = {k: packed._gather(packed.fields[k], rows, False) for k in ("target_point", "velocity", "waypoints")}
+        S, wps = config.seq_len, data["waypoints"]
+        return {"target_point": torch.stack(list(data["target_point"]), dim=1), "velocity": data["velocity"],
+                "waypoints": torch.stack([torch.stack(list(wps[i]), dim=1) for i in range(S, len(wps))], dim=1)}
+
+    def _upload(self, src, take, bounce):
+        """src[take] -> device tensor [len(take), row] (u8 as u8, f32 / f64 as f32), through the pinned bounce buffer."""
+        dt = torch.uint8 if src.dtype == np.uint8 else torch.float32
+        esz = 1 if dt == torch.uint8 else 4
+        row = int(np.prod(src.shape[1:], dtype=np.int64))
+        out = torch.empty((max(1, len(take)), row), dtype=dt, device=self.device)[:len(take)]   # (never a NULL base)
+        step = max(1, bounce.numel() // max(1, row * esz))
+        if row * esz > bounce.numel():
+            raise ValueError("one row of %d bytes does not fit the %d-byte upload buffer" % (row * esz, bounce.numel()))
+        flat = src.reshape(src.shape[0], row)
+        for r0 in range(0, len(take), step):
+            r1 = min(len(take), r0 + step)
+            stage = bounce[:(r1 - r0) * row * esz].view(dt).view(r1 - r0, row)
+            if src.dtype == np.float64:
+                stage.numpy()[...] = flat[take[r0:r1]]          # float64 -> float32, round to nearest as torch's .to()
+            else:
+                np.take(flat, take[r0:r1], axis=0, out=stage.numpy(), mode="clip")
+            out[r0:r1].copy_(stage)                            # synchronous: the buffer is free again when it returns
+        return out
+
+    def __len__(self):
+        return self.n
+
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in self.tensors.values())
+
+    def rows_of(self, sample_ids):
+        """Resident rows of global sample ids; IndexError for one that is not resident."""
+        ids = np.asarray(list(sample_ids), dtype=np.int64)
+        if ids.size and (ids.min() < 0 or ids.max() >= len(self._row_of)):
+            raise IndexError("sample index out of range")
+        rows = self._row_of[ids]
+        if ids.size and rows.min() < 0:
+            raise IndexError("sample %d is not resident on this rank" % int(ids[int(np.argmin(rows))]))
+        return rows
+
+    def gather(self, index, rows, lane_bucket=None):
+        """(engine input dict, gt) of the batch whose resident rows are `rows` (host) = `index` (int64 device tensor, the same
+        values): fresh tensors from the caching allocator and one gather launch on the current stream."""
+        from . import ops
+        B, S, dev, T = len(rows), self.seq_len, self.device, self.tensors
+        arrays = self.plan_["arrays"]
+        fields = []
+
+        def frames(names):   # frame s of sample b -> batch entry b * S + s, as MMFN._pack interleaves them
+            shape = self.shapes[names[0]]
+            out = torch.empty((B * S,) + shape, dtype=torch.float32, device=dev)
+            row = out[0].numel() if B else 0
+            for s, nm in enumerate(names):
+                fields.append(ops.gather_field(T[nm], out, row_elems=row, dst_stride=S * row, dst_offset=s * row))
+            return out
+
+        def dense(nm, shape):
+            out = torch.empty((B,) + shape, dtype=torch.float32, device=dev)
+            fields.append(ops.gather_field(T[nm], out, row_elems=out[0].numel() if B else 0))
+            return out
+
+        inp = {"image": frames(arrays[:S]), "lidar": frames(arrays[S:2 * S]), "target_point": dense("target_point", (2,)),
+               "velocity": dense("velocity", ())}
+        if self.variant == "img":
+            inp["map"] = frames(arrays[2 * S:3 * S])
+        else:
+            nm = arrays[2 * S]
+            lmax = int(self.lane_counts[rows].max()) if B else 0
+            if lane_bucket and lane_bucket > 1 and lmax % lane_bucket:
+                lmax += lane_bucket - lmax % lane_bucket       # what trainer._bucket_lanes would append, as zeros of the same launch
+            inp["lane"] = torch.empty((B, lmax) + self.shapes[nm], dtype=torch.float32, device=dev)
+            inp["lane_num"] = torch.empty(B, dtype=torch.int32, device=dev)
+            fields.append(ops.gather_field(T[nm], inp["lane"], row_elems=T[nm].shape[1], row_off=T[nm + ".row_off"],
+                                           count_out=inp["lane_num"], lmax=lmax))
+        if self.variant == "rad":
+            inp["radar"] = dense(arrays[2 * S + 1], (RADAR_ROWS, 5))
+            inp["radar_adj"] = dense(arrays[2 * S + 2], (RADAR_ROWS, RADAR_ROWS))
+        gt = dense("waypoints", tuple(T["waypoints"].shape[1:]))
+        if B:
+            ops.gather_batch(fields, index, self.n)
+        return inp, gt
+
+
+class ResidentLoader(object):
+    """PackedLoader's twin over a ResidentFrames store: same arguments, same epoch order for the same seed, but it yields finished
+    (engine input dict, gt) pairs - one gather launch per batch on the current stream, no thread, no pinned memory, no copy stream
+    (DevicePrefetcher passes `device_resident` loaders through).  The epoch's index vector is uploaded once; the lane padding of a
+    batch comes from the host's copy of the lane counts, so nothing is read back.  `lane_bucket` = k pads the lane sets to a
+    multiple of k lanes right away (Trainer's own padding then finds nothing to do).  Sampler indices are global sample ids and
+    are mapped to resident rows (IndexError for one that is not resident); without a sampler the order runs over the resident rows,
+    so a sharded store shuffles inside its shard."""
+    device_resident = True
+
+    def __init__(self, resident, batch_size, shuffle=False, sampler=None, seed=0, drop_last=False, lane_bucket=None):
+        self.resident, self.batch_size, self.shuffle, self.sampler = resident, int(batch_size), shuffle, sampler
+        self.seed, self.drop_last, self.lane_bucket = seed, drop_last, lane_bucket
+        self.epoch = 0
+
+    def _order(self):
+        return _epoch_order(len(self.resident), self.shuffle, self.sampler, self.seed, self.epoch)
+
+    def __len__(self):
+        n = len(self.sampler) if self.sampler is not None else len(self.resident)
+        return _num_batches(n, self.batch_size, self.drop_last)
+
+    def __iter__(self):
+        order = self._order()
+        self.epoch += 1
+        res = self.resident
+        rows = res.rows_of(order) if self.sampler is not None else np.asarray(order, dtype=np.int64)
+        index = torch.from_numpy(rows).to(res.device)          # the whole epoch's indices: one upload
+        pos = 0
+        for chunk in _chunks(order, self.batch_size, self.drop_last):
+            b = len(chunk)
+            yield res.gather(index[pos:pos + b], rows[pos:pos + b], self.lane_bucket)
+            pos += b
 
 
 # ------------------------------------------------------------------------------------------ collation
@@ -436,7 +674,10 @@ class DevicePrefetcher(object):
     def __init__(self, loader, device, config, variant="vec"):
         limit_host_threads()
         self.loader, self.device, self.config, self.variant = loader, torch.device(device), config, variant
-        self.stream = torch.cuda.Stream(device=self.device) if self.device.type == "cuda" else None
+        # a loader that declares `device_resident` (ResidentLoader) yields finished (engine input, gt) pairs on the consumer's
+        # stream: nothing to stage, so no copy stream either
+        self.resident = bool(getattr(loader, "device_resident", False))
+        self.stream = torch.cuda.Stream(device=self.device) if self.device.type == "cuda" and not self.resident else None
 
     def __len__(self):
         return len(self.loader)
@@ -456,6 +697,10 @@ class DevicePrefetcher(object):
         return staged, ready
 
     def __iter__(self):
+        if self.resident:
+            for item in self.loader:
+                yield item
+            return
         nxt = None
         for data in self.loader:
             cur, nxt = nxt, self._stage(data)

@@ -1305,6 +1305,33 @@ def lane_to_vector(lane, vec):
     return vec
 
 
+def gather_field(src, dst, row_elems=None, dst_stride=None, dst_offset=0, row_off=None, count_out=None, lmax=0):
+    """One mmfn_gather_field.  src: u8 / f32 [n, ...] (dense) or the samples' rows concatenated [rows, ...] (ragged, with `row_off`
+    the int64 device prefix sum [n + 1], `lmax` destination rows per sample and `count_out` int32 [B]); dst: f32.  row_elems defaults
+    to the elements of one src row; dst_stride to one sample's destination (row_elems, or lmax * row_elems); both in elements."""
+    f = _lib.GatherField()
+    if row_elems is None:
+        row_elems = src[0].numel() if src.shape[0] else int(torch.Size(src.shape[1:]).numel())
+    if dst_stride is None:
+        dst_stride = row_elems * (lmax if row_off is not None else 1)
+    f.src, f.dst, f.row_off, f.count_out = ptr(src), ptr(dst), ptr(row_off), ptr(count_out)
+    f.row_elems, f.dst_stride, f.dst_offset, f.lmax = int(row_elems), int(dst_stride), int(dst_offset), int(lmax)
+    f.src_type = _lib.GATHER_U8 if src is not None and src.dtype == torch.uint8 else _lib.GATHER_F32
+    return f
+
+
+def gather_batch(fields, index, n):
+    """Every field of one batch from a device-resident store in ONE launch (csrc/resident.hip): `fields` = gather_field(...) records
+    (at most 16), `index` = int64 device tensor [B] of sample rows, n = rows in the store.  Capturable: the kernel reads `index`."""
+    if index.dtype != torch.int64 or not index.is_contiguous():
+        raise ValueError("gather_batch: index must be a contiguous int64 tensor")
+    table = _lib.GatherTable()
+    for k, f in enumerate(fields[:_lib.GATHER_MAX_FIELDS]):
+        table.f[k] = f
+    table.n_fields = len(fields)
+    _call("mmfn_gather_batch", ctypes.byref(table), ptr(index), index.numel(), int(n), stream())
+
+
 def polyline_pool_fwd(y, out, arg, R, V, H, last):
     _call("mmfn_polyline_pool_fwd_f32", ptr(y), ptr(out), ptr(arg), R, V, H, 1 if last else 0, stream())
     return out

@@ -1,6 +1,11 @@
 """End-to-end rate of the real training loop (phase-1 frames -> loader -> pinned staging -> H2D -> fused step): pickled PRE_Data
-frames through DataLoader workers with eager launches / static-input hipGraph replay, and the packed store (data.pack_frames +
-PackedLoader) with graph replay.  Complements bench.py, whose inputs are resident in HBM."""
+frames through DataLoader workers with eager launches / static-input hipGraph replay, the packed store (data.pack_frames +
+PackedLoader) with graph replay, and the same store resident in HBM (data.ResidentFrames + ResidentLoader: one gather launch per
+batch).  Complements bench.py, whose inputs are resident in HBM.
+
+  trainer_bench.py [--dtype f32|bf16] [--modes eager,graph,packed,resident]     one child process per listed mode, in order
+  trainer_bench.py --modes packed,resident,packed,resident --dtype bf16        a repeated mode gives the run-to-run spread
+  trainer_bench.py gather                                                      child: ResidentLoader alone, for a kernel trace"""
 import json
 import os
 import pickle
@@ -33,8 +38,42 @@ def write_frames(root, n, seed=0):
             pickle.dump(s, fd)
 
 
-def run(mode, B=32, n=768, epochs=2):
-    cfg = GlobalConfig()
+def gather_bytes(res, inp, gt):
+    """(bytes read, bytes written) by the gather launch that produced (inp, gt), from the shapes: every source row once at its
+    stored width (the lane sets at their true sizes, plus index and prefix-table entries), every output element once."""
+    B = gt.shape[0]
+    read = 8 * B
+    for nm in res.plan_["arrays"]:
+        t = res.tensors[nm]
+        if nm + ".row_off" in res.tensors:
+            read += int(inp["lane_num"].sum().item()) * t.shape[1] * t.element_size() + 16 * B
+        else:
+            read += B * t.shape[1] * t.element_size()
+    read += sum(B * res.tensors[k][0].numel() * 4 for k in ("target_point", "velocity", "waypoints"))
+    written = sum(t.numel() * t.element_size() for t in inp.values()) + gt.numel() * 4
+    return read, written
+
+
+def run_gather(B=32, n=768, epochs=3, dtype="f32"):
+    """ResidentLoader alone (no training step): what a kernel trace of the gather launch should be taken on."""
+    cfg = GlobalConfig(act_dtype=dtype)
+    with tempfile.TemporaryDirectory() as tmp:
+        write_frames(tmp, n)
+        packed = D.PackedFrames(D.pack_frames(D.PRE_Data(tmp, cfg, "train"), os.path.join(tmp, "packed")))
+        res = D.ResidentFrames(packed, "cuda:0", cfg, "vec")
+        loader = D.ResidentLoader(res, batch_size=B, lane_bucket=16)
+        read = written = launches = 0
+        for _ in range(epochs):
+            for inp, gt in loader:
+                r, w = gather_bytes(res, inp, gt)
+                read, written, launches = read + r, written + w, launches + 1
+        torch.cuda.synchronize()
+        return {"gather_launches": launches, "bytes_read_per_launch": read // launches, "bytes_written_per_launch": written // launches,
+                "resident_store_bytes": res.nbytes()}
+
+
+def run(mode, B=32, n=768, epochs=2, dtype="f32"):
+    cfg = GlobalConfig(act_dtype=dtype)
     with tempfile.TemporaryDirectory() as tmp:
         write_frames(tmp, n)
         store = D.PRE_Data(tmp, cfg, "train")
@@ -47,6 +86,13 @@ def run(mode, B=32, n=768, epochs=2):
             packed = D.PackedFrames(D.pack_frames(store, os.path.join(tmp, "packed")))
             t_pack = time.time() - t_pack
             loader = D.PackedLoader(packed, batch_size=B)
+        elif mode == "resident":   # the packed store uploaded once; a batch is one gather launch on the training stream
+            packed = D.PackedFrames(D.pack_frames(store, os.path.join(tmp, "packed")))
+            t_up = time.time()
+            resident = D.ResidentFrames(packed, "cuda:0", cfg, "vec")
+            torch.cuda.synchronize()
+            t_up = time.time() - t_up
+            loader = D.ResidentLoader(resident, batch_size=B, lane_bucket=16)
         else:
             loader = torch.utils.data.DataLoader(store, batch_size=B, shuffle=False, num_workers=8, collate_fn=D.collate,
                                                  persistent_workers=True, prefetch_factor=4)
@@ -58,7 +104,7 @@ def run(mode, B=32, n=768, epochs=2):
             tr.train(net, loader, cfg, opt, graph=graph)
         torch.cuda.synchronize()
         dt = time.time() - t0
-        res = {"samples_per_s": round(epochs * n / dt, 1), "ms_per_step": round(dt / (epochs * n / B) * 1e3, 2),
+        res = {"dtype": dtype, "samples_per_s": round(epochs * n / dt, 1), "ms_per_step": round(dt / (epochs * n / B) * 1e3, 2),
                "host_threads": torch.get_num_threads()}
         # what the input side alone sustains (loader + pinned staging + H2D, no training step)
         t1 = time.time()
@@ -68,21 +114,35 @@ def run(mode, B=32, n=768, epochs=2):
         res["input_side_only_samples_per_s"] = round(n / (time.time() - t1), 1)
         if mode == "packed":
             res["pack_seconds_per_1000_frames"] = round(t_pack / n * 1000, 2)
+        if mode == "resident":
+            res["upload_seconds_per_1000_frames"] = round(t_up / n * 1000, 2)
+            res["resident_store_bytes"] = resident.nbytes()
         return res
 
 
 def main():
-    if len(sys.argv) > 1:  # child: one mode per process (loader workers and 20 GB of engine buffers do not pile up)
-        print(json.dumps(run(sys.argv[1])))
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument("mode", nargs="?", choices=["eager", "graph", "packed", "resident", "gather"],
+                    help="child: run this one mode in this process (loader workers and 20 GB of engine buffers do not pile up)")
+    ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"], help="f32 = the parity path, bf16 = the bf16 training mode")
+    ap.add_argument("--modes", default="eager,graph,packed,resident", help="parent: the modes to run, in this order; repeats allowed")
+    args = ap.parse_args()
+    if args.mode:
+        print(json.dumps(run_gather(dtype=args.dtype) if args.mode == "gather" else run(args.mode, dtype=args.dtype)))
         return
     import subprocess
-    out = {}
-    for mode in ("eager", "graph", "packed"):
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), mode], capture_output=True, text=True)
-        out[mode] = json.loads(r.stdout.strip().splitlines()[-1])
-    print(json.dumps({"workload": "Trainer.train, batch 32, 768 phase-1 frames/epoch, one MI355X; eager / graph: pickles through 8 persistent "
-                                  "DataLoader workers; packed: data.PackedLoader over the memory-mapped conversion of the same frames, "
-                                  "graph replay", **out}))
+    out = []
+    for mode in args.modes.split(","):
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), mode, "--dtype", args.dtype], capture_output=True, text=True)
+        if r.returncode:
+            sys.stderr.write(r.stderr)
+            raise SystemExit("mode %s failed with exit status %d" % (mode, r.returncode))
+        out.append({"mode": mode, **json.loads(r.stdout.strip().splitlines()[-1])})
+    print(json.dumps({"workload": "Trainer.train, batch 32, 768 phase-1 frames/epoch, one MI355X, dtype %s; eager / graph: pickles through "
+                                  "8 persistent DataLoader workers; packed: data.PackedLoader over the memory-mapped conversion of the "
+                                  "same frames, graph replay; resident: data.ResidentLoader over the same store in HBM, graph replay"
+                                  % args.dtype, "runs": out}))
 
 
 if __name__ == "__main__":
