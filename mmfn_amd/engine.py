@@ -2115,18 +2115,6 @@ class Engine(object):
             scale = self._hyper_host[0][5]
         return list(names), ops.tensor_stats(L.grads if which == "grads" else L.params, tab, scale)
 
-    def backward_and_step(self, dp=None, lr=1e-4, **adam):
-        """Backward of the last training forward + AdamW (+ the gradient all-reduces of `dp`, issued from the streams that
-        complete each readiness group while the backward is still running; the 1/world average is folded into AdamW)."""
-        if dp is None:
-            self.backward()
-            self.optimizer_step(lr=lr, **adam)
-            return
-        dp.begin()
-        self.backward(on_ready=dp.reduce)
-        dp.finish()
-        self.optimizer_step(lr=lr, grad_scale=1.0 / dp.world, **adam)
-
     def train_step(self, inp, gt, lr=1e-4, dp=None, clip_grad_norm=None, **adam):
         """One training step (see _train_step) under a single read of the requires_grad flags."""
         with self.mask_held():
@@ -2141,15 +2129,16 @@ class Engine(object):
         After accumulate_step() calls this is the last micro-step of the group: the pending sum is folded into this
         backward's gradient and AdamW sees 1 / ((pending + 1) * world) of it.  clip_grad_norm = max_norm: the step is clipped
         as torch.nn.utils.clip_grad_norm_ over every trained parameter (the norm of the averaged gradient; inf = only measure
-        it), the norm is left in last_grad_norm.  With neither, the launch sequence is the plain step's.  With the non-finite
-        guard armed (set_nonfinite_guard) the step always takes the clipped route and may be skipped on the device."""
+        it), the norm is left in last_grad_norm.  With neither, the per-group pass and the norm are no launches at all and what
+        is left is backward (+ the buckets' reductions), step count, AdamW: the plain step.  With the non-finite guard armed
+        (set_nonfinite_guard) the step always takes the clipped route and may be skipped on the device.
+
+        The hyper table is written (set_hyper: an asynchronous host-to-device copy on the compute stream, never part of a
+        capture) in front of the backward; its only readers, the norm finalize and AdamW, come after the backward."""
         self.guard_snapshot()
         clip_grad_norm = self.guarded_clip(clip_grad_norm)
         ops.rng_advance(self.rng_state)
         _, loss = self.forward(inp, True, gt)
-        if self.accum_pending == 0 and clip_grad_norm is None:
-            self.backward_and_step(dp, lr=lr, **adam)
-            return loss
         pending = self.accum_pending
         self.set_hyper(self.final_rows(lr, pending, dp, clip_grad_norm, **adam))
         self.backward_groups(ops.ACCUM_FOLD if pending else ops.ACCUM_NONE, dp, clip_grad_norm is not None)

@@ -163,7 +163,7 @@ class DataParallel(object):
                 self.pending.append(self.dist.all_reduce(g[b:e], op=self.dist.ReduceOp.SUM, async_op=True))
 
     def begin(self):
-        """Start of a step's backward (Engine.backward_and_step, GraphedStep.__call__).  A step that raised between its first
+        """Start of a step's backward (Engine.backward_groups, GraphedStep.__call__).  A step that raised between its first
         reduce() and finish() - out of memory, a failed capture that the caller retries eagerly - must not leak into the next
         one: groups still marked as reduced would be skipped (training on un-reduced gradients, or ranks issuing different
         collective sequences and hanging).  Outstanding ProcessGroup work of such a step is completed first."""
@@ -266,18 +266,23 @@ class GraphedStep(object):
             fused AdamW
     An eager step is ~2200 Python-issued launches, which makes the host the bottleneck.
 
-    variant (gradient accumulation, Engine.accumulate_step): "step" = the plain step above; "micro" = forward, backward and
-    acc += gradient per readiness group, no collective, no AdamW; "final" = the step that closes an accumulation group: the
-    per-group fold (fold=True) in front of each bucket's reduction, optional clipping (clip_grad_norm), AdamW.  k, the size r of a
-    partial group, max_norm and the learning rate only change the device hyper table (set in __call__), never the capture.
+    variant (gradient accumulation, Engine.accumulate_step): "micro" = forward, backward and acc += gradient per readiness group,
+    no collective, no AdamW; "final" = the optimizer step, which closes an accumulation group: the per-group fold (fold=True) in
+    front of each bucket's reduction, optional clipping (clip_grad_norm), AdamW; "step" (the default) = the plain step above,
+    shorthand for "final" with fold=False and no clipping (a clip_grad_norm passed with it is ignored): without fold and norm
+    Engine.group_hooks adds no launch, so the capture holds backward, reductions, step count and AdamW and nothing else (such a
+    step closes through Engine.optimizer_step, the same three launches under their public name).  k, the size r of a partial
+    group, max_norm, the learning rate and the Adam hyper-parameters only change the device hyper table, never the capture:
+    _write_rows writes the rows of this step's own lr / adam (new values: assign them, or set_hyper) in front of the capture
+    and of every replay, so a row a direct Engine.set_hyper left in the table does not reach a replayed step.
 
     Frozen parameters (Engine.trainable_mask): the capture holds the backward pruned for the requires_grad flags of that moment and
     the AdamW launch masked for them; a replay after the flags changed raises, like the checks below.
 
     Non-finite guard (Engine.set_nonfinite_guard): a "final" step captured while it is armed holds the guarded launches (the norm
     is always measured, max_norm = inf without clip_grad_norm) and replays only while it stays armed; the BatchNorm snapshot of
-    a group's first micro-step is issued by __call__ in front of the replay, outside the capture.  The plain "step" variant has
-    no norm to decide on: with the guard armed use variant="final", fold=False."""
+    a group's first micro-step is issued by __call__ in front of the replay, outside the capture.  The "step" shorthand says
+    "no norm", which the guard cannot decide on: it is refused while the guard is armed (spell it variant="final", fold=False)."""
 
     def __init__(self, engine, dp, inp, gt, lr=1e-4, warm=2, single_graph=None, variant="step", clip_grad_norm=None, fold=True,
                  **adam):
@@ -290,6 +295,8 @@ class GraphedStep(object):
         if variant == "step" and engine.nonfinite_guard:
             raise ValueError('the non-finite guard is armed: capture the optimizer step as variant="final", fold=False')
         self.engine, self.dp = engine, dp
+        if variant == "step":
+            clip_grad_norm, fold = None, False
         self.variant, self.clip, self.fold = variant, clip_grad_norm, bool(fold)
         self.lr, self.adam = lr, adam
         eng = engine
@@ -303,21 +310,17 @@ class GraphedStep(object):
                 eng.forward(inp, True, gt)
                 eng.backward()
             else:
-                eng.train_step(inp, gt, lr=lr, dp=dp, clip_grad_norm=clip_grad_norm if variant == "final" else None, **adam)
+                eng.train_step(inp, gt, lr=lr, dp=dp, clip_grad_norm=clip_grad_norm, **adam)
         torch.cuda.synchronize()
-        scale = 1.0 / (dp.world if dp is not None else 1)
-        self.scale = scale
-        if variant == "final":
-            mode = ops.ACCUM_FOLD if self.fold else ops.ACCUM_NONE
-            if self.fold:
-                eng._accum_buffer()
-            if eng.guarded_clip(clip_grad_norm) is not None:
-                eng._norm_state()
-            eng.set_hyper(eng.final_rows(lr, eng.accum_pending, dp, eng.guarded_clip(clip_grad_norm), **adam))
-        elif variant == "micro":
+        mode = ops.ACCUM_FOLD if self.fold else ops.ACCUM_NONE
+        clip = variant != "micro" and eng.guarded_clip(clip_grad_norm) is not None
+        if variant == "micro" or self.fold:
             eng._accum_buffer()
-        else:
-            eng.set_hyper(eng.hyper_rows(lr=lr, grad_scale=scale, **adam))  # the captured AdamW reads them from device memory
+        if clip:
+            eng._norm_state()
+        self.n_groups = None
+        if variant != "micro":
+            self._write_rows()   # (the capture must find them set: Engine.set_hyper refuses to change the table inside one)
         rec = self.recorder = Recorder(eng)
         if dp is not None:
             rec.extra_streams.append(dp.comm_stream)
@@ -335,43 +338,33 @@ class GraphedStep(object):
             if variant == "micro":
                 eng.backward_groups(ops.ACCUM_ADD, None, False)
                 return
-            if variant == "final":
-                n_groups = len(eng._hyper_host)
-                clip = eng.guarded_clip(clip_grad_norm) is not None
-                if dp is None or single_graph:
-                    eng.backward_groups(mode, dp, clip)
-                else:
-                    # the folds are enqueued by the hook inside the captured segments, in front of the buckets' reductions at the cuts
-                    tags = []
-                    hook, rest = eng.group_hooks(mode, False, tags.append)
-                    eng.backward_begin(on_ready=hook)
-                    for i in range(4):
-                        eng.backward_scale(3 - i, on_ready=hook)
-                        if i == 3:
-                            rest()
-                        mine, tags[:] = list(tags), []
-                        if i < 3:
-                            rec.cut(lambda mine=mine, i=i: ([dp.reduce(t) for t in mine], dp.on_stage(i)))
-                        else:
-                            rec.cut(lambda mine=mine: ([dp.reduce(t) for t in mine], dp.finish()))
-                eng.final_adam(dp, clip, n_groups)
-                return
             if dp is None or single_graph:
                 # single GPU, or collectives captured on the communication stream (forked from the stream that wrote each
                 # bucket, joined by finish()): no cut, one replay call per step
-                eng.backward_and_step(dp, lr=lr, **adam)
-                return
+                eng.backward_groups(mode, dp, clip)
             else:
+                # the folds are enqueued by the hook inside the captured segments, in front of the buckets' reductions at the cuts
+                # (no fold: the hook is the bare tags.append)
                 tags = []
-                eng.backward_begin(on_ready=tags.append)
+                hook, rest = eng.group_hooks(mode, False, tags.append)
+                eng.backward_begin(on_ready=hook)
                 for i in range(4):
-                    eng.backward_scale(3 - i, on_ready=tags.append)
+                    eng.backward_scale(3 - i, on_ready=hook)
+                    if i == 3:
+                        rest()
                     mine, tags[:] = list(tags), []
                     if i < 3:
                         rec.cut(lambda mine=mine, i=i: ([dp.reduce(t) for t in mine], dp.on_stage(i)))
                     else:   # last buckets and the wait for all of them in one cut (nothing is launched in between)
                         rec.cut(lambda mine=mine: ([dp.reduce(t) for t in mine], dp.finish()))
-            eng.optimizer_step(lr=lr, grad_scale=scale, **adam)
+            if clip or self.fold:
+                eng.final_adam(dp, clip, self.n_groups)
+            else:
+                # nothing folded, no norm: final_adam's launches are then exactly optimizer_step's, and the plain step closes
+                # under that public name, so what wraps Engine.optimizer_step (a timing seam, an injected failure) also sees
+                # the captured step.  Its set_hyper finds the rows written above and copies nothing; like every direct
+                # optimizer_step it refuses pending micro-steps, so such a capture raises here and not only at replay
+                eng.optimizer_step(lr=self.lr, grad_scale=1.0 / (dp.world if dp is not None else 1), **self.adam)
 
         pending = eng.accum_pending
         self.average = eng.average   # folded into the captured AdamW launch (or not): a replay must find the same attachment
@@ -385,12 +378,22 @@ class GraphedStep(object):
 
     def set_hyper(self, lr, **adam):
         """New learning rate / Adam hyper-parameters for the following replays (no re-capture)."""
-        self.engine.set_hyper(self.engine.hyper_rows(lr=lr, grad_scale=self.scale, **adam))
+        self.lr, self.adam = lr, adam
+
+    def _write_rows(self):
+        """This step's own rows into the device hyper table (in front of the capture and of every replay; unchanged rows are
+        no copy).  The captured AdamW launch holds the number of optimizer groups: that cannot change without a new capture."""
+        eng = self.engine
+        rows = eng.final_rows(self.lr, eng.accum_pending, self.dp, eng.guarded_clip(self.clip), **self.adam)
+        if self.n_groups not in (None, len(rows)):
+            raise ValueError("this step was captured with %d optimizer group(s), not %d: capture the step again" % (self.n_groups, len(rows)))
+        eng.set_hyper(rows)
+        self.n_groups = len(rows)
 
     def __call__(self):
         eng = self.engine
         pending = eng.accum_pending
-        if pending and (self.variant == "step" or (self.variant == "final" and not self.fold)):
+        if pending and self.variant != "micro" and not self.fold:
             raise RuntimeError("%d accumulated micro-step(s) are pending: this captured step would drop them" % pending)
         if self.variant != "micro" and eng.average is not self.average:
             raise RuntimeError("this step was captured %s; the engine now has %s: capture the step again" % (
@@ -402,8 +405,8 @@ class GraphedStep(object):
         if self.variant != "micro" and eng.nonfinite_guard != self.guard:
             raise RuntimeError("this step was captured with the non-finite guard %s; the engine now has it %s: capture the step again"
                                % (("armed", "disarmed") if self.guard else ("disarmed", "armed")))
-        if self.variant == "final":
-            eng.set_hyper(eng.final_rows(self.lr, pending, self.dp, eng.guarded_clip(self.clip), **self.adam))
+        if self.variant != "micro":
+            self._write_rows()
         eng.guard_snapshot()   # (guard armed, first micro-step of a group: the BatchNorm state a skipped step returns to)
         if self.dp is not None and not self.single_graph:
             self.dp.begin()   # (single graph: the bucket bookkeeping only ran at capture time)
@@ -430,10 +433,7 @@ class StaticBatchStep(object):
         self.engine = engine
         self.inp = {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in inp.items()}
         self.gt = gt.clone()
-        self.scale = 1.0 / (dp.world if dp is not None else 1)
         self.variant = variant
-        if variant == "step":
-            engine.set_hyper(engine.hyper_rows(lr=lr, grad_scale=self.scale, **adam))
         torch.cuda.synchronize()
         self.seg = GraphedStep(engine, dp, self.inp, self.gt, lr=lr, warm=0, variant=variant, clip_grad_norm=clip_grad_norm,
                                fold=fold, **adam)
@@ -447,11 +447,8 @@ class StaticBatchStep(object):
         return items, tuple(gt.shape)
 
     def __call__(self, inp, gt, lr=None, **adam):
-        if lr is not None:
-            if self.variant == "step":
-                self.engine.set_hyper(self.engine.hyper_rows(lr=lr, grad_scale=self.scale, **adam))
-            else:   # (the final variant sets its rows at replay: the scale depends on the pending micro-steps)
-                self.seg.lr, self.seg.adam = lr, adam
+        if lr is not None:   # (the captured step writes its rows at replay: the scale depends on the pending micro-steps)
+            self.seg.set_hyper(lr, **adam)
         for k, v in inp.items():
             if isinstance(v, torch.Tensor):
                 self.inp[k].copy_(v, non_blocking=True)

@@ -136,51 +136,20 @@ class Trainer(object):
         batches = D.DevicePrefetcher(dataloader_train, self.device, config, variant=model.variant)
         # (accumulating: one batch of look-ahead tells the epoch's last batch, which closes the partial group)
         for (args, gt), last in (_with_last(batches) if accumulating else ((b, False) for b in batches)):
-            if fused and accumulating:
-                inp = args if isinstance(args, dict) else model._pack(*args)
-                adam = dict(groups=_hyper_rows(optimizer))
-                lr = optimizer.param_groups[0]["lr"]
-                inp = _bucket_lanes(inp, lane_bucket)
-                in_group += 1
-                final = in_group == accum_steps or last
-                loss = self._accum_call(eng, dp, inp, gt, lr, adam, final, accum_steps > 1, clip_grad_norm, graph, average)
-                if final:
-                    in_group = 0
-                    if guard:
-                        window_steps += 1
-            elif fused:
+            if fused:
                 inp = args if isinstance(args, dict) else model._pack(*args)  # raw-frame batches are engine inputs already
                 # per-group (lr, beta1, beta2, eps, weight_decay): read every step, so an LR scheduler just works - they go
                 # to the device table the AdamW kernel reads, captured graphs stay valid
                 adam = dict(groups=_hyper_rows(optimizer))
                 lr = optimizer.param_groups[0]["lr"]
                 inp = _bucket_lanes(inp, lane_bucket)  # in both modes, so that eager and replayed steps are bit-identical
-                if graph:
-                    with eng.mask_held() as mask:   # one read of the flags for the signature and the replay
-                        sig = StaticBatchStep.signature(inp, gt)
-                        if average is not None:   # a capture with the average in its AdamW launch is a shape of its own
-                            sig = (sig, "average")
-                        if eng.frozen:   # ... and so is one pruned and masked for frozen parameters, per set of flags
-                            sig = (sig, mask)
-                        state = self._static_steps.pop(sig, None)
-                        if state is None:  # first batch of this shape: eager (allocates the engine's buffers for it)
-                            state = "seen"
-                            loss = eng.train_step(inp, gt, lr=lr, dp=dp, **adam)
-                        else:
-                            if state == "seen":
-                                try:
-                                    state = StaticBatchStep(eng, dp, inp, gt, lr, **adam)
-                                except RuntimeError as exc:  # a failed capture must not take the run down: this shape stays eager
-                                    import warnings
-                                    warnings.warn("hipGraph capture of the training step failed (%s); continuing with eager launches" % exc)
-                                    torch.cuda.synchronize()
-                                    state = "eager"
-                            loss = eng.train_step(inp, gt, lr=lr, dp=dp, **adam) if state == "eager" else state(inp, gt, lr=lr, **adam)
-                        self._static_steps[sig] = state  # re-inserted last: the dict is the LRU order
-                        while len(self._static_steps) > self.max_captured_shapes:
-                            _evict_lru(self._static_steps)
-                else:
-                    loss = eng.train_step(inp, gt, lr=lr, dp=dp, **adam)
+                in_group += 1
+                final = in_group == accum_steps or last   # (not accumulating: every batch is a group of its own, the plain step)
+                loss = self._step_call(eng, dp, inp, gt, lr, adam, final, accum_steps > 1, clip_grad_norm, graph, average)
+                if final:
+                    in_group = 0
+                    if guard:
+                        window_steps += 1
             else:
                 if dp is not None or isinstance(args, dict):
                     raise NotImplementedError("the autograd path takes reference-format batches on one GPU; use fused=True")
@@ -237,43 +206,44 @@ class Trainer(object):
         raise RuntimeError("all %d optimizer step(s) since the last check were skipped: the gradient is not finite in %d of %d tensors "
                            "(%s%s)" % (steps, len(bad), len(names), ", ".join(bad[:5]), ", ..." if len(bad) > 5 else ""))
 
-    def _accum_call(self, eng, dp, inp, gt, lr, adam, final, fold, clip, graph, average=None):
-        with eng.mask_held() as mask:   # one read of the flags for the signature and the step
-            return self._accum_call_held(eng, dp, inp, gt, lr, adam, final, fold, clip, graph, average, mask)
-
-    def _accum_call_held(self, eng, dp, inp, gt, lr, adam, final, fold, clip, graph, average, mask):
-        """One batch of an accumulation group: a micro-step, or (final) the step that closes the group.  graph=True: per
-        (shape, variant) the first call runs eagerly, the second captures (parallel.StaticBatchStep), later ones replay."""
-        if not graph:
+    def _step_call(self, eng, dp, inp, gt, lr, adam, final, fold, clip, graph, average=None):
+        """One batch: a micro-step of an accumulation group, or (final) the optimizer step - the one that closes the group, or
+        with fold=False and clip=None the plain step.  graph=True: per (shape, variant, fold, clipped) the first call runs eagerly
+        (it sizes the engine's buffers), the second captures (parallel.StaticBatchStep), later ones replay."""
+        def run():   # the eager step
             return eng.train_step(inp, gt, lr=lr, dp=dp, clip_grad_norm=clip, **adam) if final else eng.accumulate_step(inp, gt)
+
+        if not graph:
+            return run()
         variant = "final" if final else "micro"
-        sig = (StaticBatchStep.signature(inp, gt), variant, fold, clip is not None)
-        if average is not None and final:
-            sig = sig + ("average",)
-        if eng.nonfinite_guard and final:   # (the guarded launches are a capture of their own; micro-steps have none)
-            sig = sig + ("guard",)
-        if eng.frozen:   # (frozen parameters: the pruned backward and the masked AdamW are captures of their own, per set of flags)
-            sig = sig + (mask,)
-        state = self._static_steps.pop(sig, None)
-        if state is not None and state != "eager":
+        with eng.mask_held() as mask:   # one read of the flags for the signature and the step
+            sig = (StaticBatchStep.signature(inp, gt), variant, fold, clip is not None)
+            if average is not None and final:   # a capture with the average in its AdamW launch is a shape of its own
+                sig = sig + ("average",)
+            if eng.nonfinite_guard and final:   # (the guarded launches are a capture of their own; micro-steps have none)
+                sig = sig + ("guard",)
+            if eng.frozen:   # (frozen parameters: the pruned backward and the masked AdamW are captures of their own, per set of flags)
+                sig = sig + (mask,)
+            state = self._static_steps.pop(sig, None)
             if state == "seen":
                 try:
                     state = StaticBatchStep(eng, None if variant == "micro" else dp, inp, gt, lr, variant=variant, clip_grad_norm=clip,
                                             fold=fold, **adam)
-                except RuntimeError as exc:
+                except RuntimeError as exc:   # a failed capture must not take the run down: this shape stays eager
                     import warnings
-                    warnings.warn("hipGraph capture of the %s step failed (%s); continuing with eager launches" % (variant, exc))
+                    warnings.warn("hipGraph capture of the %s step failed (%s); continuing with eager launches" % (
+                        variant if fold or clip is not None or eng.nonfinite_guard else "training", exc))
                     torch.cuda.synchronize()
                     state = "eager"
-        if state is None or state == "eager":
-            loss = eng.train_step(inp, gt, lr=lr, dp=dp, clip_grad_norm=clip, **adam) if final else eng.accumulate_step(inp, gt)
-            state = state or "seen"
-        else:
-            state.seg.clip = clip   # max_norm lives in the hyper table: a new value is no new capture
-            loss = state(inp, gt, lr=lr, **adam)
-        self._static_steps[sig] = state
-        while len(self._static_steps) > self.max_captured_shapes:
-            _evict_lru(self._static_steps)
+            if state is None or state == "eager":   # (None: the first batch of this shape allocates the engine's buffers for it)
+                loss = run()
+                state = state or "seen"
+            else:
+                state.seg.clip = clip   # max_norm lives in the hyper table: a new value is no new capture
+                loss = state(inp, gt, lr=lr, **adam)
+            self._static_steps[sig] = state   # re-inserted last: the dict is the LRU order
+            while len(self._static_steps) > self.max_captured_shapes:
+                _evict_lru(self._static_steps)
         return loss
 
     # ------------------------------------------------------------------ validation (no grad, eval-mode BN, no dropout)

@@ -245,6 +245,86 @@ def test_graph_replay_equals_eager_bitwise():
     assert int(eb.step_count.item()) == 3
 
 
+# ------------------------------------------------------------------------------------------------ the plain step on the one route
+class _LaunchLog(object):
+    """Stands in for the ctypes handle: notes (entry point, operands) of every call that takes a stream, then makes the call."""
+
+    def __init__(self, real):
+        self._real, self.calls = real, []
+
+    def __getattr__(self, name):
+        import ctypes
+        from mmfn_amd import _lib
+        fn = getattr(self._real, name)
+        sig = _lib._SIGNATURES.get(name)
+        if sig is None or not sig[1] or sig[1][-1] is not ctypes.c_void_p:
+            return fn
+
+        def call(*a):
+            self.calls.append((name, a))
+            return fn(*a)
+        return call
+
+
+@pytest.mark.parametrize("act_dtype", ["f32", "bf16"])
+def test_plain_step_issues_no_group_pass(act_dtype, monkeypatch):
+    """No clipping, nothing pending, guard off, nothing frozen, no average: the route every step takes adds no launch to the
+    plain step - eagerly and in the default capture."""
+    from mmfn_amd import _lib
+    from mmfn_amd.parallel import GraphedStep
+    net = _net(act_dtype)
+    eng = net._engine_for()
+    inp, gt = _inputs(2, 40)
+    log = _LaunchLog(_lib.lib())
+    monkeypatch.setattr(_lib, "_lib", log)
+
+    def check(what):
+        names = [n for n, _ in log.calls]
+        for n in names:
+            assert n != "mmfn_grad_accum_f32" and not n.startswith("mmfn_grad_norm_finalize"), (what, n)
+            assert n not in ("mmfn_copy_if", "mmfn_nonfinite_slot_f32", "mmfn_step_advance_if"), (what, n)
+        assert names.count("mmfn_step_advance") == 1, what
+        assert names.count("mmfn_adamw_groups_f32") == 1 and names[-1] == "mmfn_adamw_groups_f32", what
+        assert log.calls[-1][1][9] == 0, what      # the `variant` operand: no COEF / AVG / GUARD / MASK bit
+        del log.calls[:]
+
+    eng.train_step(inp, gt)
+    torch.cuda.synchronize()
+    check("eager")
+    step = GraphedStep(eng, None, inp, gt, warm=0)
+    check("capture")
+    assert step.recorder.n_graphs == 1
+
+
+def test_default_capture_equals_final_without_fold_equals_eager_bitwise():
+    from mmfn_amd.parallel import StaticBatchStep
+    data = [_inputs(2, 50 + i) for i in range(3)]
+    lrs = [1e-4, 3e-4, 5e-5]
+    nets = [_net(), _net(), _net()]
+    for net in nets:                           # one eager step sizes the buffers for the captures
+        net._engine_for().train_step(*data[0])
+    snap = _snapshot(nets[0])
+    for net in nets:                           # ... and all three start from the same state
+        _restore(net, snap)
+    ea, eb, ec = [n._engine_for() for n in nets]
+    plain = StaticBatchStep(ea, None, data[0][0], data[0][1], lrs[0])
+    final = StaticBatchStep(eb, None, data[0][0], data[0][1], lrs[0], variant="final", fold=False)
+    for (inp, gt), lr in zip(data, lrs):
+        plain(inp, gt, lr=lr)
+        final(inp, gt, lr=lr)
+        ec.train_step(inp, gt, lr=lr)
+    torch.cuda.synchronize()
+    assert plain.seg.recorder.n_graphs == 1 and final.seg.recorder.n_graphs == 1
+    assert int(ec.step_count.item()) == int(snap[5].item()) + 3
+    for a, b, c in zip(*[_state(n) for n in nets]):
+        assert torch.equal(a, c) and torch.equal(b, c)
+    for eng, step in ((ea, plain), (eb, final)):   # neither folds: a pending micro-step would be dropped
+        eng.accumulate_step(*data[0])
+        with pytest.raises(RuntimeError, match="pending"):
+            step(*data[1])
+        eng.discard_accumulated()
+
+
 # ------------------------------------------------------------------------------------------------ trainer
 @pytest.fixture(scope="module")
 def store(tmp_path_factory):

@@ -117,7 +117,8 @@ def main():
             w._calls["k"] = 0
         ops.rng_advance(eng.rng_state)
         eng.forward(inp, True, gt)
-        eng.backward_and_step(None, lr=1e-4)
+        eng.backward()
+        eng.optimizer_step(lr=1e-4)
         proxy.muted = False
 
     body()   # eager: collects the seam labels in program order
