@@ -604,8 +604,13 @@ int mmfn_lane_to_vector_f32(const float* lane, float* vec, int64_t R, int n, voi
 
 /* ---- batch assembly from a device-resident sample store (data.ResidentFrames / ResidentLoader) ----------------------------
  * One launch gathers every field of a batch by sample index: what PackedFrames.batch, the host->device copy and the u8 -> f32
- * widening of stage_batch do.  Values are moved unchanged (u8 widened exactly); destinations are f32.
+ * widening of stage_batch do.  Values are moved unchanged (u8 widened exactly, 4-bit codes replaced by their palette entry's
+ * bits); destinations are f32.
  *   dense  (row_off == NULL): dst[b * dst_stride + dst_offset + j] = f32(src[index[b] * row_elems + j]),  j < row_elems
+ *   coded  (src_type MMFN_GATHER_PAL4, dense only): src is [n, row_elems / 2] bytes, element 2j of a row in the low nibble of
+ *          its byte j and element 2j + 1 in the high nibble; dst[b * dst_stride + dst_offset + e] = palette[code of element e],
+ *          e < row_elems.  row_elems counts DESTINATION floats and is even; palette: 16 floats in DEVICE memory, copied bit for
+ *          bit (a NaN payload or -0.0 arrives as stored).  The code buffer may start at any byte.
  *   ragged (row_off [n + 1], an ascending int64 prefix sum of rows per sample, DEVICE memory): the rows_b = row_off[i + 1] -
  *          row_off[i] source rows of sample i = index[b], each row_elems long, land at dst[b * dst_stride + dst_offset ...];
  *          the rows from rows_b up to lmax are written as +0.0 and count_out[b] = rows_b (int32; count_out may be NULL).
@@ -616,21 +621,23 @@ int mmfn_lane_to_vector_f32(const float* lane, float* vec, int64_t R, int n, voi
  * clamped into it.  Any row length and any element alignment are accepted: 16-byte accesses wherever source and destination
  * rows are misaligned alike, element accesses otherwise.
  * MMFN_EINVAL: table or index NULL, index not 8-byte aligned, n_fields outside 1..MMFN_GATHER_MAX_FIELDS, a field's src or dst
- * NULL or not aligned to its element, an unknown src_type, a negative size, B > 65535, n < 1 with work to do; nothing is
- * launched then. */
+ * NULL or not aligned to its element, an unknown src_type, a negative size, B > 65535, n < 1 with work to do; a PAL4 field
+ * whose palette is NULL or not 4-byte aligned, whose row_elems is odd or which has row_off set; nothing is launched then. */
 #define MMFN_GATHER_MAX_FIELDS 16
 #define MMFN_GATHER_U8 0
 #define MMFN_GATHER_F32 1
+#define MMFN_GATHER_PAL4 2
 typedef struct mmfn_gather_field {
   const void* src;        /* dense: [n, row_elems]; ragged: the samples' rows concatenated, [row_off[n], row_elems] */
   float* dst;
   const int64_t* row_off; /* ragged only */
   int32_t* count_out;     /* ragged only: [B] */
-  int64_t row_elems;      /* elements per source row */
+  int64_t row_elems;      /* elements per source row (PAL4: destination floats per row = twice the row's bytes) */
   int64_t dst_stride;     /* floats between the destinations of batch samples b and b + 1 */
   int64_t dst_offset;     /* floats */
-  int32_t src_type;       /* MMFN_GATHER_U8 / MMFN_GATHER_F32 */
+  int32_t src_type;       /* MMFN_GATHER_U8 / MMFN_GATHER_F32 / MMFN_GATHER_PAL4 */
   int32_t lmax;           /* ragged only: destination rows per sample */
+  const float* palette;   /* PAL4 only: 16 floats, DEVICE memory */
 } mmfn_gather_field;
 typedef struct mmfn_gather_table {
   mmfn_gather_field f[MMFN_GATHER_MAX_FIELDS];

@@ -77,13 +77,13 @@ class Conv16HaloDesc(ctypes.Structure):
                                                                 "stats_mode")]
 
 
-GATHER_MAX_FIELDS, GATHER_U8, GATHER_F32 = 16, 0, 1
+GATHER_MAX_FIELDS, GATHER_U8, GATHER_F32, GATHER_PAL4 = 16, 0, 1, 2
 
 
 class GatherField(ctypes.Structure):
     """mmfn_gather_field (include/mmfn_hip.h): one field of a batch gathered from a device-resident store."""
     _fields_ = [("src", _vp), ("dst", _vp), ("row_off", _vp), ("count_out", _vp), ("row_elems", _i64), ("dst_stride", _i64),
-                ("dst_offset", _i64), ("src_type", _i32), ("lmax", _i32)]
+                ("dst_offset", _i64), ("src_type", _i32), ("lmax", _i32), ("palette", _vp)]
 
 
 class GatherTable(ctypes.Structure):

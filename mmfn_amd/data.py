@@ -372,14 +372,75 @@ RESIDENT_RESERVE_BYTES = 24 << 30   # kept free of the store by default: the eng
 _BOUNCE_BYTES = 32 << 20            # pinned upload buffer
 
 
+# ---- 4-bit palette coding of few-valued float fields (ResidentFrames(compact=True)): exact, bit patterns compared as uint32
+def _f32_bits(rows):
+    """[n, row] uint32 view of a float array after the f64 -> f32 rounding of the upload, or None for another dtype."""
+    a = np.asarray(rows)
+    if a.dtype not in (np.float32, np.float64):
+        return None
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    return a.reshape(a.shape[0], -1).view(np.uint32)
+
+
+def _more_patterns(bits, known):
+    """Appends the f32 bit patterns of `bits` that `known` (a list) lacks; False as soon as a 17th appears."""
+    x = bits.ravel()
+    for v in known:
+        x = x[x != v]
+    while x.size:
+        if len(known) == 16:
+            return False
+        known.append(x[0])
+        x = x[x != x[0]]
+    return True
+
+
+def _palette(known):
+    """f32 [16]: the patterns in ascending uint32 order, unused slots +0.0."""
+    pal = np.zeros(16, dtype=np.uint32)
+    pal[:len(known)] = np.sort(np.asarray(known, dtype=np.uint32))
+    return pal.view(np.float32)
+
+
+def _encode_bits(bits, palette, count, out=None):
+    """uint32 [n, row] -> u8 [n, row / 2]: element 2j in the low nibble of byte j, element 2j + 1 in the high nibble."""
+    codes = np.searchsorted(palette.view(np.uint32)[:count], bits).astype(np.uint8)
+    return np.bitwise_or(codes[:, 0::2], codes[:, 1::2] << 4, out=out)
+
+
+def palette_encode(rows):
+    """(codes u8 [n, row / 2], palette f32 [16], count) of a float field [n, ...] with at most 16 distinct f32 bit patterns (+0.0
+    and -0.0, and two NaN payloads, are different entries) and an even row length; None for any other field.  f64 is rounded to
+    f32 first."""
+    bits = _f32_bits(rows)
+    known = []
+    if bits is None or bits.shape[1] % 2 or not _more_patterns(bits, known):
+        return None
+    palette = _palette(known)
+    return _encode_bits(bits, palette, len(known)), palette, len(known)
+
+
+def palette_decode(codes, palette):
+    """f32 [n, 2 * bytes per row]: the inverse of palette_encode, bit for bit."""
+    codes = np.asarray(codes, dtype=np.uint8)
+    pal = np.asarray(palette, dtype=np.float32).view(np.uint32)
+    out = np.empty((codes.shape[0], 2 * codes.shape[1]), dtype=np.uint32)
+    out[:, 0::2] = pal[codes & 15]
+    out[:, 1::2] = pal[codes >> 4]
+    return out.view(np.float32)
+
+
 class ResidentFrames(object):
     """A PackedFrames store (or the static shard `indices` of it) in device memory, reduced to what the `variant`'s engine input
     reads: camera and LiDAR frames, target point, velocity, waypoints; lane sets (vec, rad) or raster maps (img); radar and
     radar_adj (rad).  u8 stays u8 and f32 stays f32; float64 arrays and the JSON scalars are rounded to f32 on the host, the same
-    conversion stage_batch applies before its copy.  Resident row r holds sample indices[r]."""
+    conversion stage_batch applies before its copy.  Resident row r holds sample indices[r].
+    compact=True keeps every dense float field whose kept rows take at most 16 distinct f32 values (the LiDAR histogram: counts
+    clipped at 5, over 5) as 4-bit codes plus a 16-entry palette, an eighth of its f32 bytes; the gather kernel decodes it, so the
+    batches are the same bits.  A field that does not qualify stays f32."""
 
-    def __init__(self, packed, device, config, variant, indices=None, max_bytes=None):
-        plan = self.plan(packed, config, variant, indices)
+    def __init__(self, packed, device, config, variant, indices=None, max_bytes=None, compact=False):
+        plan, palettes = self._plan(packed, config, variant, indices, compact)
         self.device = torch.device(device)
         if max_bytes is None:
             if self.device.type != "cuda":
@@ -388,7 +449,8 @@ class ResidentFrames(object):
         if plan["bytes"] > max_bytes:
             raise ValueError("ResidentFrames: the store needs %d bytes of device memory, %d are available (free memory less a "
                              "%d-byte reserve for the engine's buffers unless max_bytes says otherwise); shard it with `indices` "
-                             "or stay with PackedLoader" % (plan["bytes"], max_bytes, RESIDENT_RESERVE_BYTES))
+                             "%sor stay with PackedLoader" % (plan["bytes"], max_bytes, RESIDENT_RESERVE_BYTES,
+                                                               "" if compact else ", pass compact=True "))
         self.config, self.variant, self.plan_ = config, variant, plan
         self.seq_len, self.pred_len = config.seq_len, config.pred_len
         rows = plan["rows"]
@@ -410,7 +472,9 @@ class ResidentFrames(object):
                 self.tensors[nm] = self._upload(src, take, bounce)
                 self.tensors[nm + ".row_off"] = torch.from_numpy(new_off).to(self.device)
             else:
-                self.tensors[nm] = self._upload(src, rows, bounce)
+                self.tensors[nm] = self._upload(src, rows, bounce, palettes.get(nm))
+                if nm in palettes:
+                    self.tensors[nm + ".palette"] = torch.from_numpy(palettes[nm][0]).to(self.device)
         f32 = lambda t: t.to(torch.float32).to(self.device)
         for nm, t in self._labels(packed, config, rows).items():
             self.tensors[nm] = f32(t)
@@ -418,9 +482,16 @@ class ResidentFrames(object):
 
     # ---- what goes to the device, and how many bytes: no device needed
     @classmethod
-    def plan(cls, packed, config, variant, indices=None):
-        """{"fields": {name: bytes}, "bytes": total, "arrays": [packed array names], "rows": int64 sample ids}: the kept fields
-        and the exact device bytes of ResidentFrames(packed, ..., variant, indices), computed from the schema alone."""
+    def plan(cls, packed, config, variant, indices=None, compact=False):
+        """{"fields": {name: bytes}, "bytes": total, "arrays": [packed array names], "rows": int64 sample ids, "compact": [names of
+        the fields kept as 4-bit codes]}: the kept fields and the exact device bytes of ResidentFrames(packed, ..., variant,
+        indices, compact=compact), computed from the schema alone - and, with compact=True, from one pass on the host over the
+        kept rows of every candidate field, which counts its distinct values."""
+        return cls._plan(packed, config, variant, indices, compact)[0]
+
+    @classmethod
+    def _plan(cls, packed, config, variant, indices, compact):
+        """(plan, {coded field: (palette f32 [16], count)})"""
         if variant not in ("vec", "img", "rad"):
             raise ValueError("variant must be 'vec', 'img' or 'rad', got %r" % (variant,))
         S = config.seq_len
@@ -444,7 +515,7 @@ class ResidentFrames(object):
             arrays += frames("vectormaps", 1)      # the lane set of frame 0 is the one MMFN._pack reads
         if variant == "rad":
             arrays += frames("radar", 1) + frames("radar_adj", 1)
-        fields = {}
+        fields, palettes = {}, {}
         for nm in arrays:
             src = packed.arrays[nm]
             if src.dtype not in (np.uint8, np.float32, np.float64):
@@ -456,14 +527,33 @@ class ResidentFrames(object):
                 fields[nm] = int((off[1:] - off[:-1])[rows].sum()) * row * esz
                 fields[nm + ".row_off"] = (n + 1) * 8
             else:
-                fields[nm] = n * row * esz
+                pal = cls._scan(src, rows) if compact and esz == 4 and row % 2 == 0 else None
+                if pal is not None:
+                    palettes[nm] = pal
+                    fields[nm] = n * (row // 2)
+                    fields[nm + ".palette"] = 64
+                else:
+                    fields[nm] = n * row * esz
         fields["target_point"] = n * 2 * 4
         fields["velocity"] = n * 4
         n_wp = len(packed.fields["waypoints"]["items"]) - S
         fields["waypoints"] = n * n_wp * 2 * 4
         if len(arrays) + 3 > 16:
             raise ValueError("a batch of %d fields does not fit the 16 fields of one gather launch" % (len(arrays) + 3))
-        return {"fields": fields, "bytes": int(sum(fields.values())), "arrays": arrays, "rows": rows}
+        return {"fields": fields, "bytes": int(sum(fields.values())), "arrays": arrays, "rows": rows,
+                "compact": list(palettes)}, palettes
+
+    @staticmethod
+    def _scan(src, take):
+        """Pass 1 of a coded upload: (palette, count) of src[take] ([n, ...] f32 / f64), None as soon as a 17th value appears."""
+        row = int(np.prod(src.shape[1:], dtype=np.int64))
+        flat = src.reshape(src.shape[0], row)
+        step = max(1, _BOUNCE_BYTES // max(1, row * 4))
+        known = []
+        for r0 in range(0, len(take), step):
+            if not _more_patterns(_f32_bits(flat[take[r0:r0 + step]]), known):
+                return None
+        return _palette(known), len(known)
 
     @staticmethod
     def _labels(packed, config, rows):
@@ -473,20 +563,25 @@ class ResidentFrames(object):
         return {"target_point": torch.stack(list(data["target_point"]), dim=1), "velocity": data["velocity"],
                 "waypoints": torch.stack([torch.stack(list(wps[i]), dim=1) for i in range(S, len(wps))], dim=1)}
 
-    def _upload(self, src, take, bounce):
-        """src[take] -> device tensor [len(take), row] (u8 as u8, f32 / f64 as f32), through the pinned bounce buffer."""
-        dt = torch.uint8 if src.dtype == np.uint8 else torch.float32
+    def _upload(self, src, take, bounce, palette=None):
+        """src[take] -> device tensor [len(take), row] (u8 as u8, f32 / f64 as f32), through the pinned bounce buffer.  With
+        `palette` = (f32 [16], count) the chunks are encoded into the buffer and the tensor is u8 [len(take), row / 2]: pass 2 of
+        a coded upload, the device never holds the f32 form."""
+        dt = torch.uint8 if src.dtype == np.uint8 or palette is not None else torch.float32
         esz = 1 if dt == torch.uint8 else 4
-        row = int(np.prod(src.shape[1:], dtype=np.int64))
+        n_src = int(np.prod(src.shape[1:], dtype=np.int64))
+        row = n_src // 2 if palette is not None else n_src
         out = torch.empty((max(1, len(take)), row), dtype=dt, device=self.device)[:len(take)]   # (never a NULL base)
-        step = max(1, bounce.numel() // max(1, row * esz))
+        step = max(1, bounce.numel() // max(1, n_src * 4 if palette is not None else row * esz))   # (coded: its f32 form is the chunk)
         if row * esz > bounce.numel():
             raise ValueError("one row of %d bytes does not fit the %d-byte upload buffer" % (row * esz, bounce.numel()))
-        flat = src.reshape(src.shape[0], row)
+        flat = src.reshape(src.shape[0], n_src)
         for r0 in range(0, len(take), step):
             r1 = min(len(take), r0 + step)
             stage = bounce[:(r1 - r0) * row * esz].view(dt).view(r1 - r0, row)
-            if src.dtype == np.float64:
+            if palette is not None:
+                _encode_bits(_f32_bits(flat[take[r0:r1]]), palette[0], palette[1], out=stage.numpy())
+            elif src.dtype == np.float64:
                 stage.numpy()[...] = flat[take[r0:r1]]          # float64 -> float32, round to nearest as torch's .to()
             else:
                 np.take(flat, take[r0:r1], axis=0, out=stage.numpy(), mode="clip")
@@ -522,12 +617,13 @@ class ResidentFrames(object):
             out = torch.empty((B * S,) + shape, dtype=torch.float32, device=dev)
             row = out[0].numel() if B else 0
             for s, nm in enumerate(names):
-                fields.append(ops.gather_field(T[nm], out, row_elems=row, dst_stride=S * row, dst_offset=s * row))
+                fields.append(ops.gather_field(T[nm], out, row_elems=row, dst_stride=S * row, dst_offset=s * row,
+                                               palette=T.get(nm + ".palette")))
             return out
 
         def dense(nm, shape):
             out = torch.empty((B,) + shape, dtype=torch.float32, device=dev)
-            fields.append(ops.gather_field(T[nm], out, row_elems=out[0].numel() if B else 0))
+            fields.append(ops.gather_field(T[nm], out, row_elems=out[0].numel() if B else 0, palette=T.get(nm + ".palette")))
             return out
 
         inp = {"image": frames(arrays[:S]), "lidar": frames(arrays[S:2 * S]), "target_point": dense("target_point", (2,)),

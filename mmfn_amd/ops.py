@@ -1305,18 +1305,26 @@ def lane_to_vector(lane, vec):
     return vec
 
 
-def gather_field(src, dst, row_elems=None, dst_stride=None, dst_offset=0, row_off=None, count_out=None, lmax=0):
+def gather_field(src, dst, row_elems=None, dst_stride=None, dst_offset=0, row_off=None, count_out=None, lmax=0, palette=None):
     """One mmfn_gather_field.  src: u8 / f32 [n, ...] (dense) or the samples' rows concatenated [rows, ...] (ragged, with `row_off`
     the int64 device prefix sum [n + 1], `lmax` destination rows per sample and `count_out` int32 [B]); dst: f32.  row_elems defaults
-    to the elements of one src row; dst_stride to one sample's destination (row_elems, or lmax * row_elems); both in elements."""
+    to the elements of one src row; dst_stride to one sample's destination (row_elems, or lmax * row_elems); both in elements.
+    A u8 src with `palette` (f32 [16] on the device) is a coded field: two 4-bit codes per byte, low nibble first, each replaced
+    by its palette entry; row_elems then counts destination floats (default: twice the bytes of one src row)."""
     f = _lib.GatherField()
+    coded = palette is not None and src is not None and src.dtype == torch.uint8
     if row_elems is None:
         row_elems = src[0].numel() if src.shape[0] else int(torch.Size(src.shape[1:]).numel())
+        if coded:
+            row_elems *= 2
     if dst_stride is None:
         dst_stride = row_elems * (lmax if row_off is not None else 1)
     f.src, f.dst, f.row_off, f.count_out = ptr(src), ptr(dst), ptr(row_off), ptr(count_out)
     f.row_elems, f.dst_stride, f.dst_offset, f.lmax = int(row_elems), int(dst_stride), int(dst_offset), int(lmax)
-    f.src_type = _lib.GATHER_U8 if src is not None and src.dtype == torch.uint8 else _lib.GATHER_F32
+    if coded:
+        f.src_type, f.palette = _lib.GATHER_PAL4, ptr(palette)
+    else:
+        f.src_type = _lib.GATHER_U8 if src is not None and src.dtype == torch.uint8 else _lib.GATHER_F32
     return f
 
 

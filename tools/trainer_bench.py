@@ -5,7 +5,10 @@ batch).  Complements bench.py, whose inputs are resident in HBM.
 
   trainer_bench.py [--dtype f32|bf16] [--modes eager,graph,packed,resident]     one child process per listed mode, in order
   trainer_bench.py --modes packed,resident,packed,resident --dtype bf16        a repeated mode gives the run-to-run spread
-  trainer_bench.py gather                                                      child: ResidentLoader alone, for a kernel trace"""
+  trainer_bench.py gather                                                      child: ResidentLoader alone, for a kernel trace
+  trainer_bench.py resident --compact / gather --compact                       the store with 4-bit palette codes (compact=True)
+  trainer_bench.py resident --store DIR / gather --store DIR                   keep the frames and their packed form in DIR (made
+                                                                               on first use) instead of a temporary directory"""
 import json
 import os
 import pickle
@@ -54,28 +57,52 @@ def gather_bytes(res, inp, gt):
     return read, written
 
 
-def run_gather(B=32, n=768, epochs=3, dtype="f32"):
-    """ResidentLoader alone (no training step): what a kernel trace of the gather launch should be taken on."""
+def packed_store(root, n, cfg):
+    """The packed form of write_frames(root, n), made on first use."""
+    out = os.path.join(root, "packed")
+    if not os.path.exists(os.path.join(out, "schema.json")):
+        write_frames(root, n)
+        D.pack_frames(D.PRE_Data(root, cfg, "train"), out)
+    return D.PackedFrames(out)
+
+
+def run_gather(B=32, n=768, epochs=3, dtype="f32", compact=False, store=None):
+    """ResidentLoader alone (no training step): what a kernel trace of the gather launch should be taken on.  The wall time per
+    launch (host clock over whole epochs that end in a synchronise, after a warm epoch) holds the host's work per batch too; the
+    kernel's own time is the trace's."""
     cfg = GlobalConfig(act_dtype=dtype)
     with tempfile.TemporaryDirectory() as tmp:
-        write_frames(tmp, n)
-        packed = D.PackedFrames(D.pack_frames(D.PRE_Data(tmp, cfg, "train"), os.path.join(tmp, "packed")))
-        res = D.ResidentFrames(packed, "cuda:0", cfg, "vec")
+        if store:
+            os.makedirs(store, exist_ok=True)
+        packed = packed_store(store or tmp, n, cfg)
+        res = D.ResidentFrames(packed, "cuda:0", cfg, "vec", compact=compact)
         loader = D.ResidentLoader(res, batch_size=B, lane_bucket=16)
         read = written = launches = 0
+        for inp, gt in loader:      # warm epoch: the byte counts (which read lane_num back) stay outside the timed window
+            r, w = gather_bytes(res, inp, gt)
+            read, written, launches = read + r, written + w, launches + 1
+        torch.cuda.synchronize()
+        t0 = time.time()
+        timed = 0
         for _ in range(epochs):
             for inp, gt in loader:
-                r, w = gather_bytes(res, inp, gt)
-                read, written, launches = read + r, written + w, launches + 1
+                timed += 1
         torch.cuda.synchronize()
-        return {"gather_launches": launches, "bytes_read_per_launch": read // launches, "bytes_written_per_launch": written // launches,
+        dt = time.time() - t0
+        return {"compact": bool(compact), "gather_launches": launches + timed, "wall_us_per_launch": round(dt / timed * 1e6, 1),
+                "bytes_read_per_launch": read // launches, "bytes_written_per_launch": written // launches,
                 "resident_store_bytes": res.nbytes()}
 
 
-def run(mode, B=32, n=768, epochs=2, dtype="f32"):
+def run(mode, B=32, n=768, epochs=2, dtype="f32", compact=False, store=None):
     cfg = GlobalConfig(act_dtype=dtype)
     with tempfile.TemporaryDirectory() as tmp:
-        write_frames(tmp, n)
+        if mode == "resident" and store:
+            os.makedirs(store, exist_ok=True)
+            packed_store(store, n, cfg)
+            tmp = store
+        else:
+            write_frames(tmp, n)
         store = D.PRE_Data(tmp, cfg, "train")
         torch.manual_seed(0)
         net = MMFN(cfg, "cuda:0")
@@ -87,9 +114,9 @@ def run(mode, B=32, n=768, epochs=2, dtype="f32"):
             t_pack = time.time() - t_pack
             loader = D.PackedLoader(packed, batch_size=B)
         elif mode == "resident":   # the packed store uploaded once; a batch is one gather launch on the training stream
-            packed = D.PackedFrames(D.pack_frames(store, os.path.join(tmp, "packed")))
+            packed = packed_store(tmp, n, cfg)
             t_up = time.time()
-            resident = D.ResidentFrames(packed, "cuda:0", cfg, "vec")
+            resident = D.ResidentFrames(packed, "cuda:0", cfg, "vec", compact=compact)
             torch.cuda.synchronize()
             t_up = time.time() - t_up
             loader = D.ResidentLoader(resident, batch_size=B, lane_bucket=16)
@@ -117,6 +144,7 @@ def run(mode, B=32, n=768, epochs=2, dtype="f32"):
         if mode == "resident":
             res["upload_seconds_per_1000_frames"] = round(t_up / n * 1000, 2)
             res["resident_store_bytes"] = resident.nbytes()
+            res["compact"] = bool(compact)
         return res
 
 
@@ -127,14 +155,19 @@ def main():
                     help="child: run this one mode in this process (loader workers and 20 GB of engine buffers do not pile up)")
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"], help="f32 = the parity path, bf16 = the bf16 training mode")
     ap.add_argument("--modes", default="eager,graph,packed,resident", help="parent: the modes to run, in this order; repeats allowed")
+    ap.add_argument("--compact", action="store_true", help="resident / gather: keep few-valued float fields (the LiDAR histogram) "
+                    "as 4-bit palette codes (ResidentFrames(compact=True))")
+    ap.add_argument("--store", default=None, help="resident / gather: directory that keeps the frames and their packed form between runs")
     args = ap.parse_args()
     if args.mode:
-        print(json.dumps(run_gather(dtype=args.dtype) if args.mode == "gather" else run(args.mode, dtype=args.dtype)))
+        print(json.dumps(run_gather(dtype=args.dtype, compact=args.compact, store=args.store) if args.mode == "gather"
+                         else run(args.mode, dtype=args.dtype, compact=args.compact, store=args.store)))
         return
     import subprocess
     out = []
     for mode in args.modes.split(","):
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), mode, "--dtype", args.dtype], capture_output=True, text=True)
+        extra = ["--compact"] if args.compact and mode == "resident" else []
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), mode, "--dtype", args.dtype] + extra, capture_output=True, text=True)
         if r.returncode:
             sys.stderr.write(r.stderr)
             raise SystemExit("mode %s failed with exit status %d" % (mode, r.returncode))
