@@ -648,6 +648,48 @@ int mmfn_sizeof_gather_table(void);
 /* table: HOST memory, copied into the launch (by value); n = samples in the store */
 int mmfn_gather_batch(const mmfn_gather_table* table, const int64_t* index, int B, int64_t n, void* stream);
 
+/* ---- camera colour jitter and random erasing inside the gather (data.ResidentLoader(augment=data.CameraJitter(...))) --------
+ * The camera frames of a batch, gathered by sample index as mmfn_gather_batch gathers them and augmented in the same pass:
+ * contrast, brightness and saturation blends (torchvision's ColorJitter formulas on a float image with bound 255, in this fixed
+ * order) and one erased rectangle.  Source values are 0..255 (u8, or f32 holding such values); the destination is f32.
+ * Draws, integers only.  i = clamp(index[b], 0, n - 1); id = sample_id ? sample_id[i] : i; key = mmfn_rng_key(state, 0x4A49)
+ *   (csrc/common.h: MMFN_RNG_STREAM_JITTER); k_j = mmfn_rng_u32(key, id * 8 + j) >> 8, j = 0..7 (24 bits each); u_j = k_j * 2^-24.
+ *   All n_frames frames of a sample share the eight draws: the result depends on (seed, epoch, id) alone, not on the batch, the
+ *   position in it or the rank.
+ * Arithmetic, fp32 per pixel, m = gray_mean[i * n_frames + s], clamp = min(max(., 0), 255):
+ *   f_b = fmaf(brightness, 2 u_0 - 1, 1), f_c = fmaf(contrast, 2 u_1 - 1, 1), f_s = fmaf(saturation, 2 u_2 - 1, 1)
+ *   contrast    x = clamp(fmaf(f_c, x, (1 - f_c) * m))                                   for x = r, g, b
+ *   brightness  x = clamp(f_b * x)
+ *   saturation  y = fmaf(0.114, b, fmaf(0.587, g, 0.299 * r));  x = clamp(fmaf(f_s, x, (1 - f_s) * y))
+ *   erase       iff k_3 < erase_thresh:  h = h_min + ((k_4 * (h_max - h_min + 1)) >> 24), w likewise from k_5 and the w bounds,
+ *               y0 = (k_7 * (H - h + 1)) >> 24, x0 = (k_6 * (W - w + 1)) >> 24 (64-bit integers); every channel of the pixels
+ *               in [y0, y0 + h) x [x0, x0 + w) becomes exactly m.
+ *   Strengths 0 and erase_thresh 0 give the bits of the plain gather (1 * x + 0 * m is exact).
+ * gray_mean: the mean over the STORED frame of 0.299 R + 0.587 G + 0.114 B - what the contrast blend calls for, contrast being
+ * the first stage.  index, sample_id, state and gray_mean are DEVICE memory, read by the kernel: a captured launch follows them.
+ * Any H * W and any alignment are accepted: four pixels per access (a 4-byte u8 or 16-byte f32 load per plane, 16-byte stores)
+ * where H * W is a multiple of 4 and the destination is 16-byte aligned where the source is aligned to its load, element
+ * accesses otherwise.  B == 0 returns 0 and launches nothing.
+ * MMFN_EINVAL, nothing launched: d or index NULL, index not 8-byte aligned; n_frames outside 1..MMFN_JITTER_MAX_FRAMES; a src[s]
+ * (s < n_frames), dst, gray_mean or state NULL or not aligned to its element (state, and sample_id if given: 8 bytes); src_type
+ * other than MMFN_GATHER_U8 / MMFN_GATHER_F32; H or W < 1; a strength outside [0, 1] or NaN; erase_thresh > 2^24; erase bounds
+ * outside 1 <= min <= max <= H (W) while erase_thresh > 0; B < 0, B > 65535, n < 1 with B > 0. */
+#define MMFN_JITTER_MAX_FRAMES 4
+typedef struct mmfn_camera_jitter_desc {
+  const void* src[MMFN_JITTER_MAX_FRAMES]; /* frame s of every sample: [n, 3, H, W], u8 or f32 (MMFN_GATHER_U8 / _F32), values 0..255 */
+  float* dst;                 /* [B * S, 3, H, W]; frame s of batch sample b at entry b * S + s (as MMFN._pack interleaves) */
+  const float* gray_mean;     /* DEVICE [n, S]: mean over the frame of 0.299 R + 0.587 G + 0.114 B of the STORED frame */
+  const int64_t* sample_id;   /* DEVICE [n] global sample id of resident row i, or NULL = i */
+  const uint64_t* state;      /* DEVICE [2] = {seed, epoch}: a captured launch follows it */
+  int32_t n_frames, src_type, H, W;
+  float brightness, contrast, saturation;          /* strengths in [0, 1] */
+  uint32_t erase_thresh;                           /* erase iff draw 3 < erase_thresh; round(prob * 2^24), 0 = never */
+  int32_t erase_h_min, erase_h_max, erase_w_min, erase_w_max;   /* 1 <= min <= max <= H (W); ignored when erase_thresh == 0 */
+} mmfn_camera_jitter_desc;
+int mmfn_sizeof_camera_jitter_desc(void);
+/* d: HOST memory, copied into the launch (by value); n = samples in the store */
+int mmfn_gather_camera_jitter(const mmfn_camera_jitter_desc* d, const int64_t* index, int B, int64_t n, void* stream);
+
 /* ---- VectorNet polyline max-pool + concat (model_vec.py:269-282) -------------------------------- */
 /* Lane attention of VectorNet for QUERY 0 ONLY (model_vec.py:301-324 MaskSelfAttention, of which VectornetEncoder.forward
  * :412 consumes lane 0's row alone): any number of lanes, keys >= kv_len[b] masked as the reference's -1e9 fill, kv_len 0 =

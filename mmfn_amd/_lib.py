@@ -90,6 +90,17 @@ class GatherTable(ctypes.Structure):
     _fields_ = [("f", GatherField * GATHER_MAX_FIELDS), ("n_fields", _i32), ("reserved", _i32)]
 
 
+JITTER_MAX_FRAMES = 4
+
+
+class CameraJitterDesc(ctypes.Structure):
+    """mmfn_camera_jitter_desc (include/mmfn_hip.h): the camera frames of a batch, gathered and colour-jittered in one launch."""
+    _fields_ = [("src", _vp * JITTER_MAX_FRAMES), ("dst", _vp), ("gray_mean", _vp), ("sample_id", _vp), ("state", _vp),
+                ("n_frames", _i32), ("src_type", _i32), ("H", _i32), ("W", _i32),
+                ("brightness", _f32), ("contrast", _f32), ("saturation", _f32), ("erase_thresh", ctypes.c_uint32),
+                ("erase_h_min", _i32), ("erase_h_max", _i32), ("erase_w_min", _i32), ("erase_w_max", _i32)]
+
+
 G16_NT, G16_CONV_FWD, G16_CONV_DGRAD, G16_TN, G16_CONV_WGRAD = 0, 1, 2, 3, 4
 EPI16_OUT_F32 = 1024
 EPI16_RES_F32 = 2048
@@ -155,6 +166,8 @@ def lib():
             raise MMFNLibraryError("mmfn_gpt_block_desc layout mismatch between C and ctypes")
         if handle.mmfn_sizeof_gather_table() != ctypes.sizeof(GatherTable):
             raise MMFNLibraryError("mmfn_gather_table layout mismatch between C and ctypes")
+        if handle.mmfn_sizeof_camera_jitter_desc() != ctypes.sizeof(CameraJitterDesc):
+            raise MMFNLibraryError("mmfn_camera_jitter_desc layout mismatch between C and ctypes")
         _lib = handle
     return _lib
 

@@ -106,6 +106,9 @@ __device__ __forceinline__ uint64_t mmfn_rng_key(const uint64_t* state, uint32_t
   uint64_t k = state[0] * 0xD1342543DE82EF95ull + state[1] * 0xA24BAED4963EE407ull;
   return k ^ ((uint64_t)stream << 40) ^ (uint64_t)stream * 0x9E3779B1ull;
 }
+// stream of the resident loader's camera jitter (resident.hip): the engine's dropout streams stay below 1000, and that launch reads a
+// state of its own ({seed, epoch})
+#define MMFN_RNG_STREAM_JITTER 0x4A49u
 // keep-mask scale: 0 if dropped, 1/(1-p) if kept
 __device__ __forceinline__ float mmfn_dropout_scale(uint64_t key, uint64_t idx, float p, float inv_keep) {
   float u = (float)(mmfn_rng_u32(key, idx) >> 8) * (1.0f / 16777216.0f);

@@ -1,6 +1,7 @@
 // Batch assembly from a device-resident sample store (data.ResidentFrames): one launch gathers every field of a batch by sample
 // index - what PackedFrames.batch (np.take into pinned memory), the host->device copy and the u8 -> f32 widening of stage_batch do
-// in three steps on two processors.  Values are only moved (and u8 widened, which is exact): no arithmetic.
+// in three steps on two processors.  Values are only moved (and u8 widened, which is exact): no arithmetic - except in the second
+// entry point at the end of the file, which gathers the camera field alone and colour-jitters it on the way.
 //   dense field   dst[b] = f32(src[index[b]])
 //   coded field   dst[b] = palette[4-bit codes of src[index[b]]]: a few-valued float field kept at half a byte per element
 //   ragged field  rows [off[i], off[i+1]) of the concatenated source -> dst[b, :count]; rows count..Lmax-1 = +0.0; count -> int32
@@ -163,7 +164,211 @@ __global__ __launch_bounds__(NT) void gather_batch_kernel(const GatherArgs args,
   else
     move_piece<float, 4>(reinterpret_cast<const float*>(F.src) + src0, d, valid, lo, hi, piece == 0, head, vec_ok);
 }
+
+// ---- camera colour jitter inside the gather (mmfn_gather_camera_jitter; formulas and draws: include/mmfn_hip.h) ------------------
+// The traffic of the plain gather of the camera field.  A workgroup owns 2048 consecutive pixels of ONE (sample, frame); a lane owns
+// 4 consecutive pixels per access: it loads them from each of the three channel planes (u8: three 4-byte loads, f32: three 16-byte
+// loads), so saturation has R, G and B of a pixel in registers, and writes three 16-byte stores - the lanes of a store are adjacent,
+// a wave's store covers 1 KB in one run.  (A lane owning 16 u8 pixels - one 16-byte load per plane, twelve stores with the lanes
+// 64 bytes apart, 4096 pixels per workgroup - measured 14.4 us for the camera field at batch 32 against 10.5 us this way and
+// 15.5 us for the plain gather launched on that field alone; profiles/resident_jitter_bench.txt.)
+// The frame's scalars - sample, draws, factors, rectangle, row and column of the piece's first pixel (the one 64-bit division) -
+// are the same in every lane: each lane works them out from scalar loads, no LDS and no barrier, so the pixel loads do not wait
+// behind them.  A lane finds its row and column from there with one 32-bit division per access, and only in a frame that is erased.
+constexpr int64_t JITTER_PIECE = (int64_t)NT * 8;   // pixels per workgroup
+
+struct JitterFrame {
+  float m, fc, fb, fs, tc;     // gray mean, the three factors, (1 - fc) * m
+  int32_t erase;               // 0: this sample keeps every pixel
+  int32_t y0, y1, x0, x1;      // the erased rectangle [y0, y1) x [x0, x1)
+  int32_t row;                 // row and column of the piece's first pixel
+  uint32_t col;
+};
+
+__device__ __forceinline__ float clamp255(float x) { return fminf(fmaxf(x, 0.0f), 255.0f); }
+
+template <bool ERASE>
+__device__ __forceinline__ void jitter_pixel(const JitterFrame& F, float& r, float& g, float& b, int32_t y, uint32_t x) {
+  r = clamp255(fmaf(F.fc, r, F.tc));
+  g = clamp255(fmaf(F.fc, g, F.tc));
+  b = clamp255(fmaf(F.fc, b, F.tc));
+  r = clamp255(F.fb * r);
+  g = clamp255(F.fb * g);
+  b = clamp255(F.fb * b);
+  const float ts = (1.0f - F.fs) * fmaf(0.114f, b, fmaf(0.587f, g, 0.299f * r));
+  r = clamp255(fmaf(F.fs, r, ts));
+  g = clamp255(fmaf(F.fs, g, ts));
+  b = clamp255(fmaf(F.fs, b, ts));
+  if (ERASE && y >= F.y0 && y < F.y1 && (int32_t)x >= F.x0 && (int32_t)x < F.x1) r = g = b = F.m;
+}
+
+// row / column of pixel j >= lo of the piece that starts at pixel lo = (F.row, F.col): j - lo < 2048 + 16 and F.col < W < 2^31
+__device__ __forceinline__ void jitter_pos(const JitterFrame& F, uint32_t W, int64_t j, int64_t lo, int32_t& y, uint32_t& x) {
+  const uint32_t c = F.col + (uint32_t)(j - lo);
+  const uint32_t q = c / W;
+  y = F.row + (int32_t)q;
+  x = c - q * W;
+}
+__device__ __forceinline__ void jitter_next(uint32_t W, int32_t& y, uint32_t& x) {
+  if (++x == W) { x = 0; ++y; }
+}
+
+// 4 consecutive pixels of the three planes at s, s + HW, s + 2 HW -> d, d + HW, d + 2 HW; (y, x) = row and column of the first
+template <bool ERASE>
+__device__ __forceinline__ void jitter_vec(const JitterFrame& F, const uint8_t* s, float* d, int64_t HW, int32_t y, uint32_t x, uint32_t W) {
+  const uint32_t wr = *reinterpret_cast<const uint32_t*>(s), wg = *reinterpret_cast<const uint32_t*>(s + HW),
+                 wb = *reinterpret_cast<const uint32_t*>(s + 2 * HW);
+  f32x4 vr, vg, vb;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float r = (float)((wr >> (8 * e)) & 0xffu), g = (float)((wg >> (8 * e)) & 0xffu), b = (float)((wb >> (8 * e)) & 0xffu);
+    jitter_pixel<ERASE>(F, r, g, b, y, x);
+    if (ERASE) jitter_next(W, y, x);
+    vr[e] = r; vg[e] = g; vb[e] = b;
+  }
+  *reinterpret_cast<f32x4*>(d) = vr;
+  *reinterpret_cast<f32x4*>(d + HW) = vg;
+  *reinterpret_cast<f32x4*>(d + 2 * HW) = vb;
+}
+template <bool ERASE>
+__device__ __forceinline__ void jitter_vec(const JitterFrame& F, const float* s, float* d, int64_t HW, int32_t y, uint32_t x, uint32_t W) {
+  f32x4 vr = *reinterpret_cast<const f32x4*>(s), vg = *reinterpret_cast<const f32x4*>(s + HW), vb = *reinterpret_cast<const f32x4*>(s + 2 * HW);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float r = vr[e], g = vg[e], b = vb[e];
+    jitter_pixel<ERASE>(F, r, g, b, y, x);
+    if (ERASE) jitter_next(W, y, x);
+    vr[e] = r; vg[e] = g; vb[e] = b;
+  }
+  *reinterpret_cast<f32x4*>(d) = vr;
+  *reinterpret_cast<f32x4*>(d + HW) = vg;
+  *reinterpret_cast<f32x4*>(d + 2 * HW) = vb;
+}
+
+// pixels [lo, hi) of one frame: s, d = its first plane; the planes are HW elements apart.  head = pixels before the planes' first
+// vector boundary (4 bytes for u8, 16 for f32), vec_ok = the planes and the destination are aligned alike from there on.
+template <typename T, bool ERASE>
+__device__ __forceinline__ void jitter_piece(const JitterFrame& F, const T* __restrict__ s, float* __restrict__ d, int64_t HW, uint32_t W,
+                                             int64_t lo, int64_t hi, bool first_piece, int head, bool vec_ok) {
+  const int tid = threadIdx.x;
+  auto one = [&](int64_t j) {
+    float r = src_at(s, j), g = src_at(s, j + HW), b = src_at(s, j + 2 * HW);
+    int32_t y = 0;
+    uint32_t x = 0;
+    if (ERASE) jitter_pos(F, W, j, lo, y, x);
+    jitter_pixel<ERASE>(F, r, g, b, y, x);
+    d[j] = r; d[j + HW] = g; d[j + 2 * HW] = b;
+  };
+  int64_t a = lo;
+  if (vec_ok) {
+    if (first_piece) {   // (lo == 0)
+      if (tid < head && tid < hi) one(tid);
+      a = head;
+    }
+    if (hi > a) {
+      const int64_t nv = (hi - a) / 4;
+      for (int64_t v = tid; v < nv; v += NT) {
+        const int64_t j = a + v * 4;
+        int32_t y = 0;
+        uint32_t x = 0;
+        if (ERASE) jitter_pos(F, W, j, lo, y, x);
+        jitter_vec<ERASE>(F, s + j, d + j, HW, y, x, W);
+      }
+      a += nv * 4;
+    }
+  }
+  for (int64_t j = a + tid; j < hi; j += NT) one(j);
+}
+
+__global__ __launch_bounds__(NT) void camera_jitter_kernel(const mmfn_camera_jitter_desc D, const int64_t* __restrict__ index, int64_t n) {
+  const int piece = (int)blockIdx.x, b = (int)blockIdx.y, s = (int)blockIdx.z, S = D.n_frames;
+  const int64_t HW = (int64_t)D.H * D.W, frame = 3 * HW;
+  const int esz = D.src_type == MMFN_GATHER_U8 ? 1 : 4;
+  const int align = D.src_type == MMFN_GATHER_U8 ? 4 : 16;   // bytes of a lane's load
+  JitterFrame F;                                             // (the same in every lane)
+  int64_t i = index[b];
+  i = i < 0 ? 0 : (i >= n ? n - 1 : i);
+  const uint64_t id = (uint64_t)(D.sample_id ? D.sample_id[i] : i);
+  const uint64_t key = mmfn_rng_key(D.state, MMFN_RNG_STREAM_JITTER);
+  uint32_t k[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) k[j] = mmfn_rng_u32(key, id * 8 + j) >> 8;
+  const float m = D.gray_mean[i * S + s];
+  F.m = m;
+  F.fb = fmaf(D.brightness, fmaf(2.0f, (float)k[0] * (1.0f / 16777216.0f), -1.0f), 1.0f);
+  F.fc = fmaf(D.contrast, fmaf(2.0f, (float)k[1] * (1.0f / 16777216.0f), -1.0f), 1.0f);
+  F.fs = fmaf(D.saturation, fmaf(2.0f, (float)k[2] * (1.0f / 16777216.0f), -1.0f), 1.0f);
+  F.tc = (1.0f - F.fc) * m;
+  F.erase = k[3] < D.erase_thresh;
+  F.y0 = F.y1 = F.x0 = F.x1 = F.row = 0;
+  F.col = 0;
+  if (F.erase) {
+    const int32_t h = D.erase_h_min + (int32_t)(((uint64_t)k[4] * (uint64_t)(D.erase_h_max - D.erase_h_min + 1)) >> 24);
+    const int32_t w = D.erase_w_min + (int32_t)(((uint64_t)k[5] * (uint64_t)(D.erase_w_max - D.erase_w_min + 1)) >> 24);
+    F.y0 = (int32_t)(((uint64_t)k[7] * (uint64_t)(D.H - h + 1)) >> 24);
+    F.x0 = (int32_t)(((uint64_t)k[6] * (uint64_t)(D.W - w + 1)) >> 24);
+    F.y1 = F.y0 + h;
+    F.x1 = F.x0 + w;
+    if (piece) {   // the piece's first pixel, as computed below
+      const uintptr_t sa0 = (uintptr_t)D.src[s] + (uintptr_t)(i * frame) * esz;
+      const int64_t lo0 = (int64_t)(((align - (sa0 & (align - 1))) & (align - 1)) / esz) + (int64_t)piece * JITTER_PIECE;
+      F.row = (int32_t)(lo0 / D.W);
+      F.col = (uint32_t)(lo0 % D.W);
+    }
+  }
+  const JitterFrame& f = F;
+  float* d = D.dst + ((int64_t)b * S + s) * frame;
+  const uintptr_t sa = (uintptr_t)D.src[s] + (uintptr_t)(i * frame) * esz;
+  const int head = (int)(((align - (sa & (align - 1))) & (align - 1)) / esz);
+  // vector accesses need the three source planes misaligned alike and the destination planes too (HW a multiple of 4 gives
+  // both), and the destination on a 16-byte boundary where the source is on its own
+  const bool vec_ok = HW % 4 == 0 && (((uintptr_t)(d + head)) & 15) == 0;
+  const int64_t lo = piece == 0 ? 0 : head + (int64_t)piece * JITTER_PIECE;
+  int64_t hi = head + (int64_t)(piece + 1) * JITTER_PIECE;
+  if (lo >= HW) return;
+  if (hi > HW) hi = HW;
+  const uint32_t W = (uint32_t)D.W;
+  if (D.src_type == MMFN_GATHER_U8) {
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(D.src[s]) + i * frame;
+    if (f.erase) jitter_piece<uint8_t, true>(f, src, d, HW, W, lo, hi, piece == 0, head, vec_ok);
+    else jitter_piece<uint8_t, false>(f, src, d, HW, W, lo, hi, piece == 0, head, vec_ok);
+  } else {
+    const float* src = reinterpret_cast<const float*>(D.src[s]) + i * frame;
+    if (f.erase) jitter_piece<float, true>(f, src, d, HW, W, lo, hi, piece == 0, head, vec_ok);
+    else jitter_piece<float, false>(f, src, d, HW, W, lo, hi, piece == 0, head, vec_ok);
+  }
+}
 }  // namespace
+
+extern "C" int mmfn_sizeof_camera_jitter_desc(void) { return (int)sizeof(mmfn_camera_jitter_desc); }
+
+extern "C" int mmfn_gather_camera_jitter(const mmfn_camera_jitter_desc* d, const int64_t* index, int B, int64_t n, void* stream) {
+  if (!d || !index || (uintptr_t)index % 8 || B < 0 || B > 65535) return MMFN_EINVAL;
+  if (d->n_frames < 1 || d->n_frames > MMFN_JITTER_MAX_FRAMES) return MMFN_EINVAL;
+  if (d->src_type != MMFN_GATHER_U8 && d->src_type != MMFN_GATHER_F32) return MMFN_EINVAL;
+  const int esz = d->src_type == MMFN_GATHER_F32 ? 4 : 1;
+  for (int s = 0; s < d->n_frames; ++s)
+    if (!d->src[s] || (uintptr_t)d->src[s] % esz) return MMFN_EINVAL;
+  if (!d->dst || (uintptr_t)d->dst % 4 || !d->gray_mean || (uintptr_t)d->gray_mean % 4 || !d->state || (uintptr_t)d->state % 8 ||
+      (uintptr_t)d->sample_id % 8)
+    return MMFN_EINVAL;
+  if (d->H < 1 || d->W < 1) return MMFN_EINVAL;
+  const float strength[3] = {d->brightness, d->contrast, d->saturation};
+  for (float v : strength)
+    if (!(v >= 0.0f && v <= 1.0f)) return MMFN_EINVAL;   // (a NaN fails both comparisons)
+  if (d->erase_thresh > (1u << 24)) return MMFN_EINVAL;
+  if (d->erase_thresh > 0 && (d->erase_h_min < 1 || d->erase_h_min > d->erase_h_max || d->erase_h_max > d->H || d->erase_w_min < 1 ||
+                              d->erase_w_min > d->erase_w_max || d->erase_w_max > d->W))
+    return MMFN_EINVAL;
+  if (B == 0) return 0;
+  if (n < 1) return MMFN_EINVAL;
+  const int64_t pieces = ceil_div64((int64_t)d->H * d->W, JITTER_PIECE);   // (the first piece also takes the head, as in the gather)
+  if (pieces > 0x7fffffff) return MMFN_EINVAL;
+  hipLaunchKernelGGL(camera_jitter_kernel, dim3((unsigned)pieces, (unsigned)B, (unsigned)d->n_frames), dim3(NT), 0, (hipStream_t)stream,
+                     *d, index, n);
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
 
 extern "C" int mmfn_sizeof_gather_table(void) { return (int)sizeof(mmfn_gather_table); }
 

@@ -13,7 +13,8 @@ float64 lane / radar / label tensors are narrowed to fp32 on the host before the
 
 Host-side only (numpy / torch CPU tensors + async copies): no kernels live here, and nothing here is
 part of the CPU oracle - with one exception: ResidentFrames / ResidentLoader keep the packed store in HBM and
-assemble every batch with one launch of the gather kernel (csrc/resident.hip, through ops.gather_batch).
+assemble every batch with one launch of the gather kernel (csrc/resident.hip, through ops.gather_batch), and with
+ResidentLoader(augment=CameraJitter(...)) a second one that gathers and colour-jitters the camera frames.
 """
 import os
 import pickle
@@ -430,6 +431,109 @@ def palette_decode(codes, palette):
     return out.view(np.float32)
 
 
+# ---- camera colour jitter and random erasing inside the gather (ResidentLoader(augment=CameraJitter(...)))
+# Every epoch of a resident store replays the same bytes; a host pipeline would put a transform into its Dataset.  The camera
+# field's gather has each pixel in a register on its way from u8 to f32, so the photometric augmentation happens there
+# (csrc/resident.hip, mmfn_gather_camera_jitter; formulas in include/mmfn_hip.h): no extra pass over HBM.  It is label-consistent
+# for this model - LiDAR histogram, lanes, target point and waypoints are untouched, no geometry to keep in sync.  Not built:
+# augmentation of PackedLoader / the pickle loaders, geometric, LiDAR or lane augmentation, noise, hue, a random blend order.
+RNG_STREAM_JITTER = 0x4A49      # csrc/common.h: MMFN_RNG_STREAM_JITTER
+_M32, _M64 = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
+
+
+class CameraJitter(object):
+    """Settings of the resident loader's camera augmentation.  brightness / contrast / saturation: strengths in [0, 1], the factor
+    of a sample is 1 + strength * (2 u - 1) with u uniform in [0, 1) (torchvision's ColorJitter(strength) range), applied in the
+    order contrast, brightness, saturation; erase_prob: probability that one rectangle per sample becomes the frame's gray mean,
+    its sides uniform in erase_scale = (lo, hi) as fractions of the frame's sides; seed: with the loader's epoch counter and the
+    global sample id it decides every draw.  All frames of a sample's sequence get the same draws."""
+
+    def __init__(self, brightness=0.0, contrast=0.0, saturation=0.0, erase_prob=0.0, erase_scale=(0.1, 0.3), seed=0):
+        for nm, v in (("brightness", brightness), ("contrast", contrast), ("saturation", saturation), ("erase_prob", erase_prob)):
+            if not 0.0 <= float(v) <= 1.0:     # (a NaN fails it too)
+                raise ValueError("CameraJitter: %s must lie in [0, 1], got %r" % (nm, v))
+        try:
+            lo, hi = (float(v) for v in erase_scale)
+        except (TypeError, ValueError):
+            raise ValueError("CameraJitter: erase_scale is a (lo, hi) pair of fractions, got %r" % (erase_scale,))
+        if not 0.0 < lo <= hi <= 1.0:
+            raise ValueError("CameraJitter: erase_scale needs 0 < lo <= hi <= 1, got %r" % (erase_scale,))
+        self.brightness, self.contrast, self.saturation = float(brightness), float(contrast), float(saturation)
+        self.erase_prob, self.erase_scale, self.seed = float(erase_prob), (lo, hi), int(seed)
+
+    @property
+    def erase_thresh(self):
+        """The sample is erased iff its 24-bit draw 3 is below this."""
+        return int(round(self.erase_prob * (1 << 24)))
+
+    def erase_bounds(self, side):
+        """(min, max) of the erased rectangle's extent along a side of `side` pixels."""
+        lo, hi = (min(int(side), max(1, int(round(f * side)))) for f in self.erase_scale)
+        return lo, max(lo, hi)
+
+
+def _hash32(x):
+    """mmfn_hash32 (lowbias32) of a uint64 array holding 32-bit values."""
+    x = x ^ (x >> np.uint64(16))
+    x = (x * np.uint64(0x7FEB352D)) & np.uint64(_M32)
+    x = x ^ (x >> np.uint64(15))
+    x = (x * np.uint64(0x846CA68B)) & np.uint64(_M32)
+    return x ^ (x >> np.uint64(16))
+
+
+def rng_u32(seed, step, stream, idx):
+    """mmfn_rng_u32(mmfn_rng_key({seed, step}, stream), idx) of csrc/common.h for an array of non-negative indices, restated with
+    explicit 32 / 64-bit wrap-around: uint64 array of 32-bit draws."""
+    key = ((int(seed) & _M64) * 0xD1342543DE82EF95 + (int(step) & _M64) * 0xA24BAED4963EE407) & _M64
+    key ^= ((int(stream) << 40) & _M64) ^ (int(stream) * 0x9E3779B1)
+    one = lambda v: np.asarray([v], dtype=np.uint64)
+    salt = _hash32(one(key & _M32) ^ _hash32(one(key >> 32)))       # mmfn_rng_salt
+    idx = np.asarray(idx).astype(np.uint64)
+    lo, hi = idx & np.uint64(_M32), idx >> np.uint64(32)
+    return _hash32(((lo ^ salt) + ((hi * np.uint64(0x9E3779B1)) & np.uint64(_M32))) & np.uint64(_M32))
+
+
+def jitter_draws(seed, epoch, sample_ids):
+    """int64 [len(sample_ids), 8]: the eight 24-bit draws k_0..k_7 the jitter kernel makes for global sample ids in epoch `epoch`
+    (k_j = mmfn_rng_u32(key, id * 8 + j) >> 8): brightness, contrast, saturation, erase or not, rectangle height, width, x, y."""
+    ids = np.asarray(sample_ids, dtype=np.int64).reshape(-1)
+    idx = ids[:, None].astype(np.uint64) * np.uint64(8) + np.arange(8, dtype=np.uint64)[None, :]
+    return (rng_u32(seed, epoch, RNG_STREAM_JITTER, idx) >> np.uint64(8)).astype(np.int64)
+
+
+def erase_rectangle(draws, jitter, H, W):
+    """(y0, x0, h, w) of the rectangle a sample with draws k_0..k_7 loses in an [H, W] frame, or None when it keeps every pixel."""
+    k = [int(v) for v in draws]
+    if not k[3] < jitter.erase_thresh:
+        return None
+    (h_min, h_max), (w_min, w_max) = jitter.erase_bounds(H), jitter.erase_bounds(W)
+    h = h_min + ((k[4] * (h_max - h_min + 1)) >> 24)
+    w = w_min + ((k[5] * (w_max - w_min + 1)) >> 24)
+    return (k[7] * (H - h + 1)) >> 24, (k[6] * (W - w + 1)) >> 24, h, w
+
+
+def camera_jitter_reference(frames, gray_mean, draws, jitter):
+    """What mmfn_gather_camera_jitter computes, in float64: frames [N, 3, H, W] with values 0..255, gray_mean [N] (the mean of
+    0.299 R + 0.587 G + 0.114 B over each stored frame), draws int [N, 8] (jitter_draws of each frame's sample) -> float64
+    [N, 3, H, W].  Contrast, brightness, saturation (each a blend clamped to [0, 255]), then the erased rectangle = gray_mean."""
+    x = np.array(frames, dtype=np.float64)
+    m = np.asarray(gray_mean, dtype=np.float64).reshape(-1)
+    k = np.asarray(draws, dtype=np.int64).reshape(-1, 8)
+    N, _, H, W = x.shape
+    factor = lambda strength, j: (1.0 + float(np.float32(strength)) * (2.0 * (k[:, j] / 16777216.0) - 1.0))[:, None, None, None]
+    f_b, f_c, f_s = factor(jitter.brightness, 0), factor(jitter.contrast, 1), factor(jitter.saturation, 2)
+    x = np.clip(f_c * x + (1.0 - f_c) * m[:, None, None, None], 0.0, 255.0)
+    x = np.clip(f_b * x, 0.0, 255.0)
+    gray = 0.299 * x[:, 0:1] + 0.587 * x[:, 1:2] + 0.114 * x[:, 2:3]
+    x = np.clip(f_s * x + (1.0 - f_s) * gray, 0.0, 255.0)
+    for i in range(N):
+        rect = erase_rectangle(k[i], jitter, H, W)
+        if rect is not None:
+            y0, x0, h, w = rect
+            x[i, :, y0:y0 + h, x0:x0 + w] = m[i]
+    return x
+
+
 class ResidentFrames(object):
     """A PackedFrames store (or the static shard `indices` of it) in device memory, reduced to what the `variant`'s engine input
     reads: camera and LiDAR frames, target point, velocity, waypoints; lane sets (vec, rad) or raster maps (img); radar and
@@ -604,17 +708,33 @@ class ResidentFrames(object):
             raise IndexError("sample %d is not resident on this rank" % int(ids[int(np.argmin(rows))]))
         return rows
 
-    def gather(self, index, rows, lane_bucket=None):
+    def camera_frames(self):
+        """The resident camera tensors, frame by frame ([n, 3 * H * W] u8 / f32 each), after checking that the jitter kernel can
+        take them: ValueError for a camera field that is not [3, H, W] u8 / f32."""
+        names = self.plan_["arrays"][:self.seq_len]
+        for nm in names:
+            shape, t = self.shapes[nm], self.tensors[nm]
+            if len(shape) != 3 or shape[0] != 3 or shape != self.shapes[names[0]] or t.dtype not in (torch.uint8, torch.float32) \
+                    or t.dtype != self.tensors[names[0]].dtype or nm + ".palette" in self.tensors:
+                raise ValueError("camera jitter needs [3, H, W] u8 or f32 camera frames; field %s is %s %s%s" % (
+                    nm, str(t.dtype).replace("torch.", ""), list(shape), " kept as 4-bit codes" if nm + ".palette" in self.tensors else ""))
+        return [self.tensors[nm] for nm in names]
+
+    def gather(self, index, rows, lane_bucket=None, jitter=None):
         """(engine input dict, gt) of the batch whose resident rows are `rows` (host) = `index` (int64 device tensor, the same
-        values): fresh tensors from the caching allocator and one gather launch on the current stream."""
+        values): fresh tensors from the caching allocator and one gather launch on the current stream.  `jitter` = (CameraJitter,
+        gray_mean f32 [n, S], state uint64 [2], sample_id int64 [n]), the last three on the device (ResidentLoader keeps them): the
+        camera field then goes through the jitter launch, every other field through the gather launch as before."""
         from . import ops
         B, S, dev, T = len(rows), self.seq_len, self.device, self.tensors
         arrays = self.plan_["arrays"]
         fields = []
 
-        def frames(names):   # frame s of sample b -> batch entry b * S + s, as MMFN._pack interleaves them
+        def frames(names, plain=True):   # frame s of sample b -> batch entry b * S + s, as MMFN._pack interleaves them
             shape = self.shapes[names[0]]
             out = torch.empty((B * S,) + shape, dtype=torch.float32, device=dev)
+            if not plain:
+                return out
             row = out[0].numel() if B else 0
             for s, nm in enumerate(names):
                 fields.append(ops.gather_field(T[nm], out, row_elems=row, dst_stride=S * row, dst_offset=s * row,
@@ -626,7 +746,7 @@ class ResidentFrames(object):
             fields.append(ops.gather_field(T[nm], out, row_elems=out[0].numel() if B else 0, palette=T.get(nm + ".palette")))
             return out
 
-        inp = {"image": frames(arrays[:S]), "lidar": frames(arrays[S:2 * S]), "target_point": dense("target_point", (2,)),
+        inp = {"image": frames(arrays[:S], plain=jitter is None), "lidar": frames(arrays[S:2 * S]), "target_point": dense("target_point", (2,)),
                "velocity": dense("velocity", ())}
         if self.variant == "img":
             inp["map"] = frames(arrays[2 * S:3 * S])
@@ -645,7 +765,20 @@ class ResidentFrames(object):
         gt = dense("waypoints", tuple(T["waypoints"].shape[1:]))
         if B:
             ops.gather_batch(fields, index, self.n)
+            if jitter is not None:
+                aug, gray_mean, state, sample_id = jitter
+                H, W = self.shapes[arrays[0]][1:]
+                ops.gather_camera_jitter(self.camera_frames(), inp["image"], gray_mean, state, index, self.n,
+                                         brightness=aug.brightness, contrast=aug.contrast, saturation=aug.saturation,
+                                         erase_thresh=aug.erase_thresh, erase_h=aug.erase_bounds(H), erase_w=aug.erase_bounds(W),
+                                         sample_id=sample_id)
         return inp, gt
+
+
+def _as_i64(v):
+    """The int64 with the bits of v mod 2^64 (the kernel reads the state as uint64)."""
+    v = int(v) & _M64
+    return v - (1 << 64) if v >> 63 else v
 
 
 class ResidentLoader(object):
@@ -655,13 +788,39 @@ class ResidentLoader(object):
     batch comes from the host's copy of the lane counts, so nothing is read back.  `lane_bucket` = k pads the lane sets to a
     multiple of k lanes right away (Trainer's own padding then finds nothing to do).  Sampler indices are global sample ids and
     are mapped to resident rows (IndexError for one that is not resident); without a sampler the order runs over the resident rows,
-    so a sharded store shuffles inside its shard."""
+    so a sharded store shuffles inside its shard.
+    `augment` = CameraJitter(...) jitters the camera frames inside their gather (a second launch per batch, for that field alone):
+    the draws depend on (augment.seed, this loader's epoch counter, global sample id) only, so a shard draws what the full store
+    would.  The loader then holds the frames' gray means (f32 [n, S], computed once here), the {seed, epoch} state the kernel reads
+    and the sample ids, all on the device and none of them in the store.  None (the default) is the plain path, bit for bit; build
+    validation loaders without it.  PackedLoader and the pickle loaders are not augmented."""
     device_resident = True
 
-    def __init__(self, resident, batch_size, shuffle=False, sampler=None, seed=0, drop_last=False, lane_bucket=None):
+    def __init__(self, resident, batch_size, shuffle=False, sampler=None, seed=0, drop_last=False, lane_bucket=None, augment=None):
         self.resident, self.batch_size, self.shuffle, self.sampler = resident, int(batch_size), shuffle, sampler
         self.seed, self.drop_last, self.lane_bucket = seed, drop_last, lane_bucket
         self.epoch = 0
+        self.augment = augment
+        if augment is not None:
+            if not isinstance(augment, CameraJitter):
+                raise TypeError("augment takes a CameraJitter (or None), got %r" % (augment,))
+            # what the jitter launch reads besides the store lives HERE: the store, its plan and its byte count stay as they are
+            self.gray_mean = self._gray_mean(resident)
+            self.jitter_state = torch.zeros(2, dtype=torch.int64, device=resident.device)      # {seed, epoch}, the kernel's uint64[2]
+            self.sample_id = torch.from_numpy(np.ascontiguousarray(resident.indices, dtype=np.int64)).to(resident.device)
+
+    @staticmethod
+    def _gray_mean(resident, chunk=32):
+        """f32 [n, S] on the device: the mean of 0.299 R + 0.587 G + 0.114 B over every stored camera frame - the mean the contrast
+        blend (the first stage) calls for.  Once per loader, a chunk of frames at a time, accumulated in fp64."""
+        cams = resident.camera_frames()
+        out = torch.empty(max(1, resident.n), len(cams), dtype=torch.float32, device=resident.device)[:resident.n]   # (never a NULL base)
+        weights = torch.tensor([0.299, 0.587, 0.114], dtype=torch.float64, device=resident.device)
+        for s, t in enumerate(cams):
+            for r0 in range(0, resident.n, chunk):
+                x = t[r0:r0 + chunk].view(-1, 3, t.shape[1] // 3).to(torch.float64)
+                out[r0:r0 + chunk, s] = (x.mean(dim=2) * weights).sum(dim=1).to(torch.float32)
+        return out
 
     def _order(self):
         return _epoch_order(len(self.resident), self.shuffle, self.sampler, self.seed, self.epoch)
@@ -672,6 +831,10 @@ class ResidentLoader(object):
 
     def __iter__(self):
         order = self._order()
+        jitter = None
+        if self.augment is not None:     # the epoch counter that seeds the shuffle also keys the draws
+            self.jitter_state.copy_(torch.tensor([_as_i64(self.augment.seed), _as_i64(self.epoch)], dtype=torch.int64))
+            jitter = (self.augment, self.gray_mean, self.jitter_state, self.sample_id)
         self.epoch += 1
         res = self.resident
         rows = res.rows_of(order) if self.sampler is not None else np.asarray(order, dtype=np.int64)
@@ -679,7 +842,10 @@ class ResidentLoader(object):
         pos = 0
         for chunk in _chunks(order, self.batch_size, self.drop_last):
             b = len(chunk)
-            yield res.gather(index[pos:pos + b], rows[pos:pos + b], self.lane_bucket)
+            if jitter is None:
+                yield res.gather(index[pos:pos + b], rows[pos:pos + b], self.lane_bucket)
+            else:
+                yield res.gather(index[pos:pos + b], rows[pos:pos + b], self.lane_bucket, jitter=jitter)
             pos += b
 
 

@@ -1340,6 +1340,34 @@ def gather_batch(fields, index, n):
     _call("mmfn_gather_batch", ctypes.byref(table), ptr(index), index.numel(), int(n), stream())
 
 
+def gather_camera_jitter(srcs, dst, gray_mean, state, index, n, brightness=0.0, contrast=0.0, saturation=0.0, erase_thresh=0,
+                         erase_h=(1, 1), erase_w=(1, 1), sample_id=None):
+    """The camera frames of one batch gathered AND colour-jittered in one launch (csrc/resident.hip, mmfn_gather_camera_jitter).
+    srcs: 1..4 tensors [n, 3, H, W] (or [n, 3 * H * W] with dst giving H, W), all u8 or all f32 with values 0..255: frame s of every
+    sample; dst: f32 [B * S, 3, H, W], frame s of batch sample b at entry b * S + s; gray_mean: f32 [n, S] device; state: uint64
+    (or int64) [2] device = {seed, epoch}; index: int64 device [B]; sample_id: int64 device [n] or None (= the row).  Strengths in
+    [0, 1]; erase_thresh = round(prob * 2^24); erase_h / erase_w = (min, max) of the erased rectangle's sides in pixels.
+    Capturable: index, state and sample_id are read by the kernel."""
+    if index.dtype != torch.int64 or not index.is_contiguous():
+        raise ValueError("gather_camera_jitter: index must be a contiguous int64 tensor")
+    if not 1 <= len(srcs) <= _lib.JITTER_MAX_FRAMES:
+        raise ValueError("gather_camera_jitter: 1..%d frames per sample, got %d" % (_lib.JITTER_MAX_FRAMES, len(srcs)))
+    if dst.dim() != 4 or dst.shape[1] != 3 or dst.dtype != torch.float32 or not dst.is_contiguous():
+        raise ValueError("gather_camera_jitter: dst must be a contiguous f32 [B * S, 3, H, W] tensor")
+    d = _lib.CameraJitterDesc()
+    for s, t in enumerate(srcs):
+        if t is not None and (t.dtype != srcs[0].dtype or not t.is_contiguous() or (t.shape[0] and t[0].numel() != dst[0].numel())):
+            raise ValueError("gather_camera_jitter: every source is a contiguous [n, 3, H, W] tensor of one dtype")
+        d.src[s] = ptr(t)
+    d.dst, d.gray_mean, d.sample_id, d.state = ptr(dst), ptr(gray_mean), ptr(sample_id), ptr(state)
+    d.n_frames, d.H, d.W = len(srcs), dst.shape[2], dst.shape[3]
+    d.src_type = _lib.GATHER_U8 if srcs[0] is not None and srcs[0].dtype == torch.uint8 else _lib.GATHER_F32
+    d.brightness, d.contrast, d.saturation, d.erase_thresh = float(brightness), float(contrast), float(saturation), int(erase_thresh)
+    (d.erase_h_min, d.erase_h_max), (d.erase_w_min, d.erase_w_max) = (int(v) for v in erase_h), (int(v) for v in erase_w)
+    _call("mmfn_gather_camera_jitter", ctypes.byref(d), ptr(index), index.numel(), int(n), stream())
+    return dst
+
+
 def polyline_pool_fwd(y, out, arg, R, V, H, last):
     _call("mmfn_polyline_pool_fwd_f32", ptr(y), ptr(out), ptr(arg), R, V, H, 1 if last else 0, stream())
     return out
