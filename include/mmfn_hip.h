@@ -690,6 +690,69 @@ int mmfn_sizeof_camera_jitter_desc(void);
 /* d: HOST memory, copied into the launch (by value); n = samples in the store */
 int mmfn_gather_camera_jitter(const mmfn_camera_jitter_desc* d, const int64_t* index, int B, int64_t n, void* stream);
 
+/* ---- LiDAR dropout, lane dropout and map noise inside the gather (data.ResidentLoader(augment=data.Augment(...))) -----------
+ * The bird's-eye-view inputs of a batch, gathered by sample index as mmfn_gather_batch gathers them and augmented in the same
+ * pass; `parts` says which of the three fields the launch carries (MMFN_AUGMENT_LIDAR | _LANES | _TARGET), the others' members
+ * are not read.  The LiDAR image itself and the raster map are not rotated or shifted (that needs resampling): not built.
+ * Draws, integers only.  i = clamp(index[b], 0, n - 1); id = sample_id ? sample_id[i] : i; key_X = mmfn_rng_key(state, stream X)
+ *   with lidar_state for the streams MMFN_RNG_STREAM_LIDAR (0x4C44) and _LIDAR_CELL (0x4C43) and map_state for _MAP (0x4D50)
+ *   and _LANE (0x4C4E) (csrc/common.h); state = {seed, epoch}.  Everything depends on (seed, epoch, id) alone.
+ * LiDAR, field [C, H, W], the n_frames frames of a sample alike, src_type U8 / F32 / PAL4 (one palette per frame):
+ *   k_j = mmfn_rng_u32(key_LIDAR, id * 8 + j) >> 8; k_0..k_2 are reserved.  Erased iff k_3 < erase_thresh, the rectangle from
+ *   k_4..k_7 and the erase bounds as in mmfn_gather_camera_jitter: every channel of its cells becomes +0.0.  Element
+ *   e = (c * H + y) * W + x is dropped iff (mmfn_rng_u32(key_LIDAR_CELL, id * (C * H * W) + e) >> 8) < cell_thresh (a 64-bit
+ *   index, wrapping): +0.0.  A kept element carries the source's bits (u8 widened, PAL4 the palette entry's bits): occupancy
+ *   features, no rescaling - the output is exact.
+ * Lanes, ragged field of rows [lane_nodes, 5], node = [x, y, f2, f3, f4], f32:
+ *   k_j = mmfn_rng_u32(key_MAP, id * 8 + j) >> 8, w_j = fmaf(2, k_j * 2^-24, -1) (exact in fp32), j = 0..4.
+ *   tx = shift * w_0, ty = shift * w_1, theta = yaw_rad * w_2, c = cosf(theta), s = sinf(theta) (the accurate functions).
+ *   A node whose five features are all zero is padding and is copied; any other node gets
+ *   x' = fmaf(c, x, fmaf(-s, y, tx)), y' = fmaf(s, x, fmaf(c, y, ty)), f2..f4 copied.  With shift == 0 and yaw_rad == 0 every
+ *   node is copied bit for bit.
+ *   Dropout over the first rows = min(rows_b, lmax) stored lanes: lane 0 (the query of the lane attention) is always kept, lane
+ *   j >= 1 is dropped iff (mmfn_rng_u32(key_LANE, id * 65536 + j) >> 8) < lane_thresh; the kept lanes land in stored order at
+ *   destination rows 0..kept-1, the rows from there to lmax are +0.0, lane_count_out[b] = rows_b - dropped (may be NULL).
+ *   lmax <= MMFN_AUGMENT_MAX_LANES: the kept-lane map of a sample is held in 8 KB of LDS.
+ * Target point [n, 2] f32: tp' = (fmaf(target_shift, w_3, tp_x), fmaf(target_shift, w_4, tp_y)); copied when target_shift == 0.
+ * index, sample_id, the states and lane_row_off are DEVICE memory, read by the kernel: a captured launch follows them.  Any
+ * size and alignment: 16-byte accesses where a LiDAR row's source and destination are misaligned alike, element accesses
+ * otherwise.  B == 0 returns 0 and launches nothing.
+ * MMFN_EINVAL, nothing launched: d or index NULL, index not 8-byte aligned; parts 0 or with unknown bits; a pointer of an active
+ * part NULL or not aligned to its element (states, sample_id, lane_row_off: 8 bytes; lane_count_out may be NULL); n_frames
+ * outside 1..MMFN_AUGMENT_MAX_FRAMES; an unknown src_type; PAL4 with a NULL palette or odd C * H * W; C, H or W < 1; a threshold
+ * above 2^24; erase bounds outside 1 <= min <= max <= H (W) while erase_thresh > 0; shift or target_shift outside [0, 64] or
+ * NaN; yaw_rad outside [0, pi/4 + 1e-6] or NaN; lane_nodes < 1; lmax < 0 or > MMFN_AUGMENT_MAX_LANES; B < 0, B > 65535, n < 1
+ * with B > 0. */
+#define MMFN_AUGMENT_MAX_FRAMES 4
+#define MMFN_AUGMENT_MAX_LANES 4096
+#define MMFN_AUGMENT_LIDAR 1
+#define MMFN_AUGMENT_LANES 2
+#define MMFN_AUGMENT_TARGET 4
+typedef struct mmfn_gather_augment_desc {
+  const int64_t* sample_id;     /* DEVICE [n] global sample id of resident row i, or NULL = i */
+  const void* lidar_src[MMFN_AUGMENT_MAX_FRAMES];        /* frame s of every sample: [n, C, H, W] u8 / f32, or [n, C*H*W / 2] codes */
+  const float* lidar_palette[MMFN_AUGMENT_MAX_FRAMES];   /* PAL4 only: 16 floats per frame, DEVICE memory */
+  float* lidar_dst;             /* [B * S, C, H, W]; frame s of batch sample b at entry b * S + s */
+  const uint64_t* lidar_state;  /* DEVICE [2] = {seed, epoch} */
+  const float* lane_src;        /* the samples' lanes concatenated: [lane_row_off[n], lane_nodes, 5] */
+  const int64_t* lane_row_off;  /* DEVICE [n + 1] */
+  float* lane_dst;              /* [B, lmax, lane_nodes, 5] */
+  int32_t* lane_count_out;      /* [B], or NULL */
+  const float* target_src;      /* [n, 2] */
+  float* target_dst;            /* [B, 2] */
+  const uint64_t* map_state;    /* DEVICE [2] = {seed, epoch}: lanes and target point */
+  int32_t parts;                /* MMFN_AUGMENT_LIDAR | MMFN_AUGMENT_LANES | MMFN_AUGMENT_TARGET */
+  int32_t n_frames, src_type, C, H, W;
+  uint32_t cell_thresh, erase_thresh;                           /* round(prob * 2^24), 0 = never */
+  int32_t erase_h_min, erase_h_max, erase_w_min, erase_w_max;   /* ignored when erase_thresh == 0 */
+  int32_t lane_nodes, lmax;
+  uint32_t lane_thresh;
+  float shift, yaw_rad, target_shift;                           /* metres, radians, metres */
+} mmfn_gather_augment_desc;
+int mmfn_sizeof_gather_augment_desc(void);
+/* d: HOST memory, copied into the launch (by value); n = samples in the store */
+int mmfn_gather_augment(const mmfn_gather_augment_desc* d, const int64_t* index, int B, int64_t n, void* stream);
+
 /* ---- VectorNet polyline max-pool + concat (model_vec.py:269-282) -------------------------------- */
 /* Lane attention of VectorNet for QUERY 0 ONLY (model_vec.py:301-324 MaskSelfAttention, of which VectornetEncoder.forward
  * :412 consumes lane 0's row alone): any number of lanes, keys >= kv_len[b] masked as the reference's -1e9 fill, kv_len 0 =

@@ -101,6 +101,23 @@ class CameraJitterDesc(ctypes.Structure):
                 ("erase_h_min", _i32), ("erase_h_max", _i32), ("erase_w_min", _i32), ("erase_w_max", _i32)]
 
 
+AUGMENT_MAX_FRAMES, AUGMENT_MAX_LANES = 4, 4096
+AUGMENT_LIDAR, AUGMENT_LANES, AUGMENT_TARGET = 1, 2, 4
+
+
+class GatherAugmentDesc(ctypes.Structure):
+    """mmfn_gather_augment_desc (include/mmfn_hip.h): the LiDAR frames, the lane set and the target point of a batch, gathered
+    and augmented in one launch."""
+    _fields_ = [("sample_id", _vp), ("lidar_src", _vp * AUGMENT_MAX_FRAMES), ("lidar_palette", _vp * AUGMENT_MAX_FRAMES),
+                ("lidar_dst", _vp), ("lidar_state", _vp), ("lane_src", _vp), ("lane_row_off", _vp), ("lane_dst", _vp),
+                ("lane_count_out", _vp), ("target_src", _vp), ("target_dst", _vp), ("map_state", _vp),
+                ("parts", _i32), ("n_frames", _i32), ("src_type", _i32), ("C", _i32), ("H", _i32), ("W", _i32),
+                ("cell_thresh", ctypes.c_uint32), ("erase_thresh", ctypes.c_uint32),
+                ("erase_h_min", _i32), ("erase_h_max", _i32), ("erase_w_min", _i32), ("erase_w_max", _i32),
+                ("lane_nodes", _i32), ("lmax", _i32), ("lane_thresh", ctypes.c_uint32),
+                ("shift", _f32), ("yaw_rad", _f32), ("target_shift", _f32)]
+
+
 G16_NT, G16_CONV_FWD, G16_CONV_DGRAD, G16_TN, G16_CONV_WGRAD = 0, 1, 2, 3, 4
 EPI16_OUT_F32 = 1024
 EPI16_RES_F32 = 2048
@@ -168,6 +185,8 @@ def lib():
             raise MMFNLibraryError("mmfn_gather_table layout mismatch between C and ctypes")
         if handle.mmfn_sizeof_camera_jitter_desc() != ctypes.sizeof(CameraJitterDesc):
             raise MMFNLibraryError("mmfn_camera_jitter_desc layout mismatch between C and ctypes")
+        if handle.mmfn_sizeof_gather_augment_desc() != ctypes.sizeof(GatherAugmentDesc):
+            raise MMFNLibraryError("mmfn_gather_augment_desc layout mismatch between C and ctypes")
         _lib = handle
     return _lib
 

@@ -109,6 +109,12 @@ __device__ __forceinline__ uint64_t mmfn_rng_key(const uint64_t* state, uint32_t
 // stream of the resident loader's camera jitter (resident.hip): the engine's dropout streams stay below 1000, and that launch reads a
 // state of its own ({seed, epoch})
 #define MMFN_RNG_STREAM_JITTER 0x4A49u
+// streams of the resident loader's LiDAR dropout (per-sample draws, per-element draws) and map noise (per-sample draws, per-lane
+// draws): mmfn_gather_augment, each part with a {seed, epoch} state of its own
+#define MMFN_RNG_STREAM_LIDAR 0x4C44u
+#define MMFN_RNG_STREAM_LIDAR_CELL 0x4C43u
+#define MMFN_RNG_STREAM_MAP 0x4D50u
+#define MMFN_RNG_STREAM_LANE 0x4C4Eu
 // keep-mask scale: 0 if dropped, 1/(1-p) if kept
 __device__ __forceinline__ float mmfn_dropout_scale(uint64_t key, uint64_t idx, float p, float inv_keep) {
   float u = (float)(mmfn_rng_u32(key, idx) >> 8) * (1.0f / 16777216.0f);

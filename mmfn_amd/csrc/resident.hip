@@ -1,7 +1,8 @@
 // Batch assembly from a device-resident sample store (data.ResidentFrames): one launch gathers every field of a batch by sample
 // index - what PackedFrames.batch (np.take into pinned memory), the host->device copy and the u8 -> f32 widening of stage_batch do
 // in three steps on two processors.  Values are only moved (and u8 widened, which is exact): no arithmetic - except in the second
-// entry point at the end of the file, which gathers the camera field alone and colour-jitters it on the way.
+// entry point at the end of the file, which gathers the camera field alone and colour-jitters it on the way, and in the third, which
+// gathers the LiDAR frames, the lane set and the target point and drops cells and lanes and moves the map on the way.
 //   dense field   dst[b] = f32(src[index[b]])
 //   coded field   dst[b] = palette[4-bit codes of src[index[b]]]: a few-valued float field kept at half a byte per element
 //   ragged field  rows [off[i], off[i+1]) of the concatenated source -> dst[b, :count]; rows count..Lmax-1 = +0.0; count -> int32
@@ -338,7 +339,352 @@ __global__ __launch_bounds__(NT) void camera_jitter_kernel(const mmfn_camera_jit
     else jitter_piece<float, false>(f, src, d, HW, W, lo, hi, piece == 0, head, vec_ok);
   }
 }
+
+// ---- LiDAR dropout, lane dropout and map noise inside the gather (mmfn_gather_augment; draws and formulas: include/mmfn_hip.h) ---
+// The traffic of the plain gather of these fields, which leave its table.  Workgroups [0, S * pieces) of a sample own a piece of ONE
+// LiDAR (sample, frame) row, cut as gather_batch_kernel cuts it (16 KB of f32 / u8 source, 4 KB of codes through the same LDS turn)
+// and masked in registers between load and store: a hash per element for the cell dropout, a rectangle test for the erasure.  The
+// frame's scalars are the same in every lane, worked out from scalar loads as in the jitter.  An element's (y, x) is needed in an
+// erased sample only: the offset of the piece's first element in its [H, W] plane is one 64-bit division per workgroup, a lane adds
+// its distance from there, steps back by H * W where that runs past the plane's end (a piece is no longer than a plane; a plane
+// shorter than a piece takes a 32-bit remainder instead) and divides by W once per access.
+// The first workgroup of a sample owns its lane set and its target point (first, so that its chain of dependent loads runs beside
+// the LiDAR pieces and not after them): keep bits of 256 lanes at a time, a prefix sum over the
+// workgroup (ballot per wave, the waves' counts through LDS) that writes the kept lanes' numbers into a map in LDS, then one node
+// (five floats) per lane and step through the kept lanes, then the zero rows.  A few KB per sample.
+constexpr int AUG_MAX_LANES = MMFN_AUGMENT_MAX_LANES;
+
+struct AugmentGrid {
+  int32_t map_blocks;    // 1: workgroup 0 of a sample is its map workgroup (lane set, target point); 0: no such part
+  int32_t pieces;        // workgroups per LiDAR (sample, frame) row; n_frames * pieces of them follow
+  int32_t batch;
+};
+
+struct LidarFrame {
+  uint64_t key, base;          // key of the element draws; id * C * H * W
+  uint32_t cell_thresh;
+  int32_t erase;               // 0: no rectangle in this sample
+  uint32_t y0, y1, x0, x1;     // the erased rectangle [y0, y1) x [x0, x1)
+  uint32_t H, W, HW;
+  uint32_t p0;                 // offset of the piece's first element in its plane
+  int32_t wrap_once;           // H * W >= a piece's elements: p0 + distance passes the plane's end at most once
+};
+
+// row / column of element j >= lo of the piece whose first element lo sits at plane offset F.p0: j - lo < 16 K + 32, HW < 2^31
+__device__ __forceinline__ void lidar_pos(const LidarFrame& F, int64_t j, int64_t lo, uint32_t& y, uint32_t& x) {
+  uint32_t p = F.p0 + (uint32_t)(j - lo);
+  if (F.wrap_once) {
+    if (p >= F.HW) p -= F.HW;
+  } else {
+    p %= F.HW;
+  }
+  const uint32_t q = p / F.W;
+  y = q;
+  x = p - q * F.W;
+}
+__device__ __forceinline__ void lidar_next(const LidarFrame& F, uint32_t& y, uint32_t& x) {
+  if (++x == F.W) {
+    x = 0;
+    if (++y == F.H) y = 0;
+  }
+}
+// element e of the row, value v, at (y, x) of its plane: v's bits, or +0.0
+__device__ __forceinline__ float lidar_mask(const LidarFrame& F, float v, int64_t e, uint32_t y, uint32_t x) {
+  bool drop = F.erase && y >= F.y0 && y < F.y1 && x >= F.x0 && x < F.x1;
+  if (F.cell_thresh) drop |= (mmfn_rng_u32(F.key, F.base + (uint64_t)e) >> 8) < F.cell_thresh;
+  return drop ? 0.0f : v;
+}
+
+// V consecutive elements from row element j on, at s -> d
+__device__ __forceinline__ void lidar_vec(const LidarFrame& F, const float* s, float* d, int64_t j, uint32_t y, uint32_t x) {
+  f32x4 v = *reinterpret_cast<const f32x4*>(s);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    v[e] = lidar_mask(F, v[e], j + e, y, x);
+    if (F.erase) lidar_next(F, y, x);
+  }
+  *reinterpret_cast<f32x4*>(d) = v;
+}
+__device__ __forceinline__ void lidar_vec(const LidarFrame& F, const uint8_t* s, float* d, int64_t j, uint32_t y, uint32_t x) {
+  const uint4 u = *reinterpret_cast<const uint4*>(s);
+  const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    f32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      v[e] = lidar_mask(F, (float)((w[k] >> (8 * e)) & 0xffu), j + 4 * k + e, y, x);
+      if (F.erase) lidar_next(F, y, x);
+    }
+    *reinterpret_cast<f32x4*>(d + 4 * k) = v;
+  }
+}
+
+// elements [lo, hi) of one LiDAR row: move_piece with the mask between load and store (a dense row: nothing to zero-fill)
+template <typename T, int V>
+__device__ __forceinline__ void lidar_piece(const LidarFrame& F, const T* __restrict__ s, float* __restrict__ d, int64_t lo, int64_t hi,
+                                            bool first_piece, int head, bool vec_ok) {
+  const int tid = threadIdx.x;
+  auto one = [&](int64_t j) {
+    uint32_t y = 0, x = 0;
+    if (F.erase) lidar_pos(F, j, lo, y, x);
+    d[j] = lidar_mask(F, src_at(s, j), j, y, x);
+  };
+  int64_t a = lo;
+  if (vec_ok) {
+    if (first_piece) {   // (lo == 0)
+      if (tid < head && tid < hi) one(tid);
+      a = head;
+    }
+    if (hi > a) {
+      const int64_t nv = (hi - a) / V;
+      for (int64_t v = tid; v < nv; v += NT) {
+        const int64_t j = a + v * V;
+        uint32_t y = 0, x = 0;
+        if (F.erase) lidar_pos(F, j, lo, y, x);
+        lidar_vec(F, s + j, d + j, j, y, x);
+      }
+      a += nv * V;
+    }
+  }
+  for (int64_t j = a + tid; j < hi; j += NT) one(j);
+}
+
+// source BYTES [lo, hi) of one coded LiDAR row: move_piece_pal4 with the mask after the palette lookup; F.p0 belongs to element 2 lo
+__device__ __forceinline__ void lidar_piece_pal4(const LidarFrame& F, const uint8_t* __restrict__ s, float* __restrict__ d,
+                                                 const float* __restrict__ palette, float* pal, uint4* stage, int64_t lo, int64_t hi,
+                                                 bool first_piece, int head, bool vec_ok) {
+  const int tid = threadIdx.x;
+  auto one = [&](int64_t j) {   // byte j: elements 2 j and 2 j + 1
+    const uint32_t c = s[j];
+    uint32_t y = 0, x = 0;
+    if (F.erase) lidar_pos(F, 2 * j, 2 * lo, y, x);
+    d[2 * j] = lidar_mask(F, pal[c & 15u], 2 * j, y, x);
+    if (F.erase) lidar_next(F, y, x);
+    d[2 * j + 1] = lidar_mask(F, pal[(c >> 4) & 15u], 2 * j + 1, y, x);
+  };
+  int64_t a = lo;
+  int nv = 0;                                       // 16-byte accesses of this piece: 0..NT, the same for every lane
+  if (vec_ok) {
+    if (first_piece) a = head;
+    if (hi > a) nv = (int)((hi - a) / 16);
+  }
+  if (tid < 16) pal[tid] = palette[tid];
+  if (tid < nv) stage[tid] = *reinterpret_cast<const uint4*>(s + a + (int64_t)tid * 16);
+  __syncthreads();
+  if (vec_ok) {
+    if (first_piece && tid < head && tid < hi) one(tid);
+    const uint16_t* codes = reinterpret_cast<const uint16_t*>(stage);
+    const int base = (tid >> 6) * 1024 + 2 * (tid & 63);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int byte = base + 128 * k;              // even, and nv * 16 is too: byte + 1 is inside as well
+      if (byte < nv * 16) {
+        const uint32_t c = codes[byte >> 1];
+        const int64_t j = 2 * (a + byte);
+        uint32_t y = 0, x = 0;
+        if (F.erase) lidar_pos(F, j, 2 * lo, y, x);
+        f32x4 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          v[e] = lidar_mask(F, pal[(c >> (4 * e)) & 15u], j + e, y, x);
+          if (F.erase) lidar_next(F, y, x);
+        }
+        *reinterpret_cast<f32x4*>(d + j) = v;
+      }
+    }
+    a += (int64_t)nv * 16;
+  }
+  for (int64_t j = a + tid; j < hi; j += NT) one(j);
+}
+
+__device__ __forceinline__ float draw_pm1(uint32_t k) { return fmaf(2.0f, (float)k * (1.0f / 16777216.0f), -1.0f); }
+
+// the lane set and the target point of batch sample b = store row i, global id `id`: every thread of the workgroup calls this
+__device__ __forceinline__ void map_block(const mmfn_gather_augment_desc& D, int b, int64_t i, uint64_t id, uint16_t* kept_lane,
+                                          int* wave_count, float* rigid) {
+  const int tid = threadIdx.x;
+  const uint64_t key = mmfn_rng_key(D.map_state, MMFN_RNG_STREAM_MAP);
+  if ((D.parts & MMFN_AUGMENT_TARGET) && tid < 2) {
+    const float t = D.target_src[i * 2 + tid];
+    const float w = draw_pm1(mmfn_rng_u32(key, id * 8 + 3 + tid) >> 8);
+    D.target_dst[(int64_t)b * 2 + tid] = D.target_shift != 0.0f ? fmaf(D.target_shift, w, t) : t;
+  }
+  if (!(D.parts & MMFN_AUGMENT_LANES)) return;      // (the same for every lane of the workgroup)
+  const bool moved = D.shift != 0.0f || D.yaw_rad != 0.0f;
+  if (tid == 0 && moved) {                          // once per workgroup: the library's sinf / cosf are not short
+    const float theta = D.yaw_rad * draw_pm1(mmfn_rng_u32(key, id * 8 + 2) >> 8);
+    rigid[0] = cosf(theta);
+    rigid[1] = sinf(theta);
+    rigid[2] = D.shift * draw_pm1(mmfn_rng_u32(key, id * 8 + 0) >> 8);
+    rigid[3] = D.shift * draw_pm1(mmfn_rng_u32(key, id * 8 + 1) >> 8);
+  }
+  const int64_t o0 = D.lane_row_off[i];
+  const int64_t stored = D.lane_row_off[i + 1] - o0;
+  const int rows = (int)(stored < 0 ? 0 : (stored > D.lmax ? (int64_t)D.lmax : stored));
+  // the kept-lane map: kept_lane[r] = stored lane that lands at destination row r
+  const uint64_t lane_key = mmfn_rng_key(D.map_state, MMFN_RNG_STREAM_LANE);
+  int kept = 0;
+  for (int j0 = 0; j0 < rows; j0 += NT) {
+    const int j = j0 + tid;
+    const bool keep = j < rows && (j == 0 || !((mmfn_rng_u32(lane_key, id * 65536 + (uint64_t)j) >> 8) < D.lane_thresh));
+    const uint64_t wave_keep = __ballot(keep);
+    if ((tid & 63) == 0) wave_count[tid >> 6] = __popcll(wave_keep);
+    __syncthreads();
+    int before = kept, all = 0;
+#pragma unroll
+    for (int w = 0; w < NT / 64; ++w) {
+      const int c = wave_count[w];
+      if (w < (tid >> 6)) before += c;
+      all += c;
+    }
+    if (keep) kept_lane[before + __popcll(wave_keep & ((1ull << (tid & 63)) - 1ull))] = (uint16_t)j;
+    kept += all;
+    __syncthreads();                                // wave_count is rewritten in the next round; kept_lane and rigid are read below
+  }
+  if (rows == 0) __syncthreads();                   // (rigid)
+  if (tid == 0 && D.lane_count_out) D.lane_count_out[b] = (int32_t)(stored - (rows - kept));
+  const float c = moved ? rigid[0] : 1.0f, s = moved ? rigid[1] : 0.0f, tx = moved ? rigid[2] : 0.0f, ty = moved ? rigid[3] : 0.0f;
+  const int nodes = D.lane_nodes;
+  const int64_t row_elems = (int64_t)nodes * 5;
+  float* d = D.lane_dst + (int64_t)b * D.lmax * row_elems;
+  const float* src = D.lane_src + o0 * row_elems;
+  const int n_nodes = kept * nodes;                 // <= 4096 * lane_nodes, checked on the host to fit 31 bits
+  for (int e = tid; e < n_nodes; e += NT) {
+    const int r = e / nodes, nd = e - r * nodes;
+    const float* p = src + (int64_t)kept_lane[r] * row_elems + nd * 5;
+    float* q = d + (int64_t)e * 5;
+    float x = p[0], y = p[1];
+    const float f2 = p[2], f3 = p[3], f4 = p[4];
+    if (moved && !(x == 0.0f && y == 0.0f && f2 == 0.0f && f3 == 0.0f && f4 == 0.0f)) {   // an all-zero node is padding
+      const float xr = fmaf(c, x, fmaf(-s, y, tx));
+      y = fmaf(s, x, fmaf(c, y, ty));
+      x = xr;
+    }
+    q[0] = x; q[1] = y; q[2] = f2; q[3] = f3; q[4] = f4;
+  }
+  const int64_t total = (int64_t)D.lmax * row_elems;
+  for (int64_t j = (int64_t)kept * row_elems + tid; j < total; j += NT) d[j] = 0.0f;
+}
+
+__global__ __launch_bounds__(NT) void gather_augment_kernel(const mmfn_gather_augment_desc D, const AugmentGrid G,
+                                                            const int64_t* __restrict__ index, int64_t n) {
+  __shared__ float pal[16];
+  __shared__ uint4 stage[NT];                     // a coded piece's 16-byte accesses, turned for the stores
+  __shared__ uint16_t kept_lane[AUG_MAX_LANES];
+  __shared__ int wave_count[NT / 64];
+  __shared__ float rigid[4];
+  int blk = (int)(blockIdx.x / (unsigned)G.batch);
+  const int b = (int)(blockIdx.x % (unsigned)G.batch);                                                // the sample is the fastest index
+  int64_t i = index[b];
+  i = i < 0 ? 0 : (i >= n ? n - 1 : i);
+  const uint64_t id = (uint64_t)(D.sample_id ? D.sample_id[i] : i);
+  if (blk < G.map_blocks) {
+    map_block(D, b, i, id, kept_lane, wave_count, rigid);
+    return;
+  }
+  blk -= G.map_blocks;
+  const int s = blk / G.pieces, piece = blk - s * G.pieces, S = D.n_frames;
+  const int64_t HW = (int64_t)D.H * D.W, row = HW * D.C;
+  const int esz = D.src_type == MMFN_GATHER_F32 ? 4 : 1;
+  const bool pal4 = D.src_type == MMFN_GATHER_PAL4;
+  // in BYTES of the source (PAL4: a byte is two elements), as gather_batch_kernel cuts its rows
+  const int64_t per = pal4 ? PIECE_BYTES_PAL4 : PIECE_BYTES / esz;
+  const int64_t total = pal4 ? row >> 1 : row;
+  const uintptr_t sa = (uintptr_t)D.lidar_src[s] + (uintptr_t)(i * total) * esz;
+  const int head = (int)(((16 - (sa & 15)) & 15) / esz);
+  float* d = D.lidar_dst + ((int64_t)b * S + s) * row;
+  const bool vec_ok = (((uintptr_t)(d + (pal4 ? 2 * head : head))) & 15) == 0;
+  const int64_t lo = piece == 0 ? 0 : head + (int64_t)piece * per;
+  int64_t hi = head + (int64_t)(piece + 1) * per;
+  if (lo >= total) return;                        // (the same for every lane of the workgroup)
+  if (hi > total) hi = total;
+  LidarFrame F;                                   // (the same in every lane)
+  F.key = mmfn_rng_key(D.lidar_state, MMFN_RNG_STREAM_LIDAR_CELL);
+  F.base = id * (uint64_t)row;
+  F.cell_thresh = D.cell_thresh;
+  F.H = (uint32_t)D.H; F.W = (uint32_t)D.W; F.HW = (uint32_t)HW;
+  F.y0 = F.y1 = F.x0 = F.x1 = F.p0 = 0;
+  F.wrap_once = HW >= (pal4 ? 2 * per : per) + 32;
+  const uint64_t key = mmfn_rng_key(D.lidar_state, MMFN_RNG_STREAM_LIDAR);
+  F.erase = (mmfn_rng_u32(key, id * 8 + 3) >> 8) < D.erase_thresh;
+  if (F.erase) {
+    uint32_t k[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) k[j] = mmfn_rng_u32(key, id * 8 + 4 + j) >> 8;
+    const uint32_t h = (uint32_t)D.erase_h_min + (uint32_t)(((uint64_t)k[0] * (uint64_t)(D.erase_h_max - D.erase_h_min + 1)) >> 24);
+    const uint32_t w = (uint32_t)D.erase_w_min + (uint32_t)(((uint64_t)k[1] * (uint64_t)(D.erase_w_max - D.erase_w_min + 1)) >> 24);
+    F.y0 = (uint32_t)(((uint64_t)k[3] * (uint64_t)(F.H - h + 1)) >> 24);
+    F.x0 = (uint32_t)(((uint64_t)k[2] * (uint64_t)(F.W - w + 1)) >> 24);
+    F.y1 = F.y0 + h;
+    F.x1 = F.x0 + w;
+    F.p0 = (uint32_t)((pal4 ? 2 * lo : lo) % HW);
+  }
+  const LidarFrame& f = F;
+  if (pal4)
+    lidar_piece_pal4(f, reinterpret_cast<const uint8_t*>(D.lidar_src[s]) + i * total, d, D.lidar_palette[s], pal, stage, lo, hi, piece == 0,
+                     head, vec_ok);
+  else if (D.src_type == MMFN_GATHER_U8)
+    lidar_piece<uint8_t, 16>(f, reinterpret_cast<const uint8_t*>(D.lidar_src[s]) + i * row, d, lo, hi, piece == 0, head, vec_ok);
+  else
+    lidar_piece<float, 4>(f, reinterpret_cast<const float*>(D.lidar_src[s]) + i * row, d, lo, hi, piece == 0, head, vec_ok);
+}
 }  // namespace
+
+extern "C" int mmfn_sizeof_gather_augment_desc(void) { return (int)sizeof(mmfn_gather_augment_desc); }
+
+extern "C" int mmfn_gather_augment(const mmfn_gather_augment_desc* d, const int64_t* index, int B, int64_t n, void* stream) {
+  if (!d || !index || (uintptr_t)index % 8 || B < 0 || B > 65535) return MMFN_EINVAL;
+  const int all = MMFN_AUGMENT_LIDAR | MMFN_AUGMENT_LANES | MMFN_AUGMENT_TARGET;
+  if (d->parts == 0 || (d->parts & ~all) || (uintptr_t)d->sample_id % 8) return MMFN_EINVAL;
+  AugmentGrid g = {0, 0, B};
+  if (d->parts & MMFN_AUGMENT_LIDAR) {
+    if (d->n_frames < 1 || d->n_frames > MMFN_AUGMENT_MAX_FRAMES) return MMFN_EINVAL;
+    if (d->src_type != MMFN_GATHER_U8 && d->src_type != MMFN_GATHER_F32 && d->src_type != MMFN_GATHER_PAL4) return MMFN_EINVAL;
+    if (d->C < 1 || d->H < 1 || d->W < 1) return MMFN_EINVAL;
+    const int64_t plane = (int64_t)d->H * d->W;
+    if (plane > 0x3fffffff || plane * d->C > ((int64_t)1 << 40)) return MMFN_EINVAL;   // (plane offsets are 32-bit in the kernel)
+    const int64_t row = plane * d->C;
+    const bool pal4 = d->src_type == MMFN_GATHER_PAL4;
+    const int esz = d->src_type == MMFN_GATHER_F32 ? 4 : 1;
+    if (pal4 && (row & 1)) return MMFN_EINVAL;
+    for (int s = 0; s < d->n_frames; ++s) {
+      if (!d->lidar_src[s] || (uintptr_t)d->lidar_src[s] % esz) return MMFN_EINVAL;
+      if (pal4 && (!d->lidar_palette[s] || (uintptr_t)d->lidar_palette[s] % 4)) return MMFN_EINVAL;
+    }
+    if (!d->lidar_dst || (uintptr_t)d->lidar_dst % 4 || !d->lidar_state || (uintptr_t)d->lidar_state % 8) return MMFN_EINVAL;
+    if (d->cell_thresh > (1u << 24) || d->erase_thresh > (1u << 24)) return MMFN_EINVAL;
+    if (d->erase_thresh > 0 && (d->erase_h_min < 1 || d->erase_h_min > d->erase_h_max || d->erase_h_max > d->H || d->erase_w_min < 1 ||
+                                d->erase_w_min > d->erase_w_max || d->erase_w_max > d->W))
+      return MMFN_EINVAL;
+    // (the first piece also takes the < 16-byte head, as in the gather)
+    g.pieces = (int32_t)(pal4 ? ceil_div64(row / 2, PIECE_BYTES_PAL4) : ceil_div64(row * esz, PIECE_BYTES));
+  }
+  if (d->parts & (MMFN_AUGMENT_LANES | MMFN_AUGMENT_TARGET))
+    if (!d->map_state || (uintptr_t)d->map_state % 8) return MMFN_EINVAL;
+  if (d->parts & MMFN_AUGMENT_LANES) {
+    if (!d->lane_src || (uintptr_t)d->lane_src % 4 || !d->lane_dst || (uintptr_t)d->lane_dst % 4 || !d->lane_row_off ||
+        (uintptr_t)d->lane_row_off % 8 || (uintptr_t)d->lane_count_out % 4)
+      return MMFN_EINVAL;
+    if (d->lane_nodes < 1 || d->lane_nodes > (1 << 18) || d->lmax < 0 || d->lmax > MMFN_AUGMENT_MAX_LANES) return MMFN_EINVAL;
+    if (d->lane_thresh > (1u << 24)) return MMFN_EINVAL;
+    if (!(d->shift >= 0.0f && d->shift <= 64.0f)) return MMFN_EINVAL;                  // (a NaN fails both comparisons)
+    if (!(d->yaw_rad >= 0.0f && d->yaw_rad <= 0.78539816339744831f + 1e-6f)) return MMFN_EINVAL;
+  }
+  if (d->parts & MMFN_AUGMENT_TARGET) {
+    if (!d->target_src || (uintptr_t)d->target_src % 4 || !d->target_dst || (uintptr_t)d->target_dst % 4) return MMFN_EINVAL;
+    if (!(d->target_shift >= 0.0f && d->target_shift <= 64.0f)) return MMFN_EINVAL;
+  }
+  if (B == 0) return 0;
+  if (n < 1) return MMFN_EINVAL;
+  g.map_blocks = (d->parts & (MMFN_AUGMENT_LANES | MMFN_AUGMENT_TARGET)) ? 1 : 0;
+  const int64_t blocks = (d->parts & MMFN_AUGMENT_LIDAR ? (int64_t)g.pieces * d->n_frames : 0) + g.map_blocks;
+  if (blocks * B > 0x7fffffff) return MMFN_EINVAL;
+  // the sample is the fastest index of the 1-D grid, as in a gather launch with a coded field (see mmfn_gather_batch)
+  hipLaunchKernelGGL(gather_augment_kernel, dim3((unsigned)(blocks * B)), dim3(NT), 0, (hipStream_t)stream, *d, g, index, n);
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
 
 extern "C" int mmfn_sizeof_camera_jitter_desc(void) { return (int)sizeof(mmfn_camera_jitter_desc); }
 

@@ -435,13 +435,59 @@ def palette_decode(codes, palette):
 # Every epoch of a resident store replays the same bytes; a host pipeline would put a transform into its Dataset.  The camera
 # field's gather has each pixel in a register on its way from u8 to f32, so the photometric augmentation happens there
 # (csrc/resident.hip, mmfn_gather_camera_jitter; formulas in include/mmfn_hip.h): no extra pass over HBM.  It is label-consistent
-# for this model - LiDAR histogram, lanes, target point and waypoints are untouched, no geometry to keep in sync.  Not built:
-# augmentation of PackedLoader / the pickle loaders, geometric, LiDAR or lane augmentation, noise, hue, a random blend order.
+# for this model - LiDAR histogram, lanes, target point and waypoints are untouched, no geometry to keep in sync.
+# The bird's-eye-view inputs are augmented the same way (Augment(lidar=LidarDropout(...), map=MapNoise(...)); one more launch,
+# mmfn_gather_augment): cells and one rectangle of the LiDAR histogram dropped, lanes dropped, the lane set moved rigidly and the
+# target point shifted, as localisation noise moves them in closed loop.  Not built: augmentation of PackedLoader / the pickle
+# loaders, rotating or shifting the LiDAR image or the raster map (both need resampling and would disagree with the un-shifted
+# camera), radar, velocity or waypoint noise, hue, a random blend order.
 RNG_STREAM_JITTER = 0x4A49      # csrc/common.h: MMFN_RNG_STREAM_JITTER
+RNG_STREAM_LIDAR = 0x4C44       # MMFN_RNG_STREAM_LIDAR: a sample's LiDAR draws (erase or not, the rectangle)
+RNG_STREAM_LIDAR_CELL = 0x4C43  # MMFN_RNG_STREAM_LIDAR_CELL: one draw per LiDAR element
+RNG_STREAM_MAP = 0x4D50         # MMFN_RNG_STREAM_MAP: a sample's map draws (shift, yaw, target shift)
+RNG_STREAM_LANE = 0x4C4E        # MMFN_RNG_STREAM_LANE: one draw per lane
+AUGMENT_MAX_LANES = 4096        # include/mmfn_hip.h: MMFN_AUGMENT_MAX_LANES
 _M32, _M64 = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
 
 
-class CameraJitter(object):
+def _prob(owner, nm, v, hi=1.0):
+    """float(v) in [0, hi], ValueError otherwise (a NaN fails it too)."""
+    if not 0.0 <= float(v) <= hi:
+        raise ValueError("%s: %s must lie in [0, %g], got %r" % (owner, nm, hi, v))
+    return float(v)
+
+
+def _thresh(p):
+    """A 24-bit draw below this happens with probability p."""
+    return int(round(p * (1 << 24)))
+
+
+class _Erasing(object):
+    """The one-rectangle-per-sample settings CameraJitter and LidarDropout share: erase_prob, erase_scale = (lo, hi) fractions of
+    the frame's sides."""
+
+    def _set_erase(self, erase_prob, erase_scale):
+        owner = type(self).__name__
+        try:
+            lo, hi = (float(v) for v in erase_scale)
+        except (TypeError, ValueError):
+            raise ValueError("%s: erase_scale is a (lo, hi) pair of fractions, got %r" % (owner, erase_scale))
+        if not 0.0 < lo <= hi <= 1.0:
+            raise ValueError("%s: erase_scale needs 0 < lo <= hi <= 1, got %r" % (owner, erase_scale))
+        self.erase_prob, self.erase_scale = _prob(owner, "erase_prob", erase_prob), (lo, hi)
+
+    @property
+    def erase_thresh(self):
+        """The sample is erased iff its 24-bit draw 3 is below this."""
+        return _thresh(self.erase_prob)
+
+    def erase_bounds(self, side):
+        """(min, max) of the erased rectangle's extent along a side of `side` pixels."""
+        lo, hi = (min(int(side), max(1, int(round(f * side)))) for f in self.erase_scale)
+        return lo, max(lo, hi)
+
+
+class CameraJitter(_Erasing):
     """Settings of the resident loader's camera augmentation.  brightness / contrast / saturation: strengths in [0, 1], the factor
     of a sample is 1 + strength * (2 u - 1) with u uniform in [0, 1) (torchvision's ColorJitter(strength) range), applied in the
     order contrast, brightness, saturation; erase_prob: probability that one rectangle per sample becomes the frame's gray mean,
@@ -449,27 +495,77 @@ class CameraJitter(object):
     global sample id it decides every draw.  All frames of a sample's sequence get the same draws."""
 
     def __init__(self, brightness=0.0, contrast=0.0, saturation=0.0, erase_prob=0.0, erase_scale=(0.1, 0.3), seed=0):
-        for nm, v in (("brightness", brightness), ("contrast", contrast), ("saturation", saturation), ("erase_prob", erase_prob)):
-            if not 0.0 <= float(v) <= 1.0:     # (a NaN fails it too)
-                raise ValueError("CameraJitter: %s must lie in [0, 1], got %r" % (nm, v))
-        try:
-            lo, hi = (float(v) for v in erase_scale)
-        except (TypeError, ValueError):
-            raise ValueError("CameraJitter: erase_scale is a (lo, hi) pair of fractions, got %r" % (erase_scale,))
-        if not 0.0 < lo <= hi <= 1.0:
-            raise ValueError("CameraJitter: erase_scale needs 0 < lo <= hi <= 1, got %r" % (erase_scale,))
-        self.brightness, self.contrast, self.saturation = float(brightness), float(contrast), float(saturation)
-        self.erase_prob, self.erase_scale, self.seed = float(erase_prob), (lo, hi), int(seed)
+        self.brightness, self.contrast, self.saturation = (_prob("CameraJitter", nm, v) for nm, v in (
+            ("brightness", brightness), ("contrast", contrast), ("saturation", saturation)))
+        self._set_erase(erase_prob, erase_scale)
+        self.seed = int(seed)
 
     @property
-    def erase_thresh(self):
-        """The sample is erased iff its 24-bit draw 3 is below this."""
-        return int(round(self.erase_prob * (1 << 24)))
+    def active(self):
+        return bool(self.brightness or self.contrast or self.saturation or self.erase_thresh)
 
-    def erase_bounds(self, side):
-        """(min, max) of the erased rectangle's extent along a side of `side` pixels."""
-        lo, hi = (min(int(side), max(1, int(round(f * side)))) for f in self.erase_scale)
-        return lo, max(lo, hi)
+
+class LidarDropout(_Erasing):
+    """Settings of the resident loader's LiDAR augmentation.  cell_prob: probability that an element of the [C, H, W] histogram
+    becomes 0 (each channel of a cell on its own); erase_prob: probability that one rectangle per sample loses every channel, its
+    sides as in CameraJitter.  Kept elements keep their bits: occupancy features are not rescaled.  All frames of a sample's
+    sequence get the same draws, decided by (seed, loader epoch, global sample id)."""
+
+    def __init__(self, cell_prob=0.0, erase_prob=0.0, erase_scale=(0.1, 0.3), seed=0):
+        self.cell_prob = _prob("LidarDropout", "cell_prob", cell_prob)
+        self._set_erase(erase_prob, erase_scale)
+        self.seed = int(seed)
+
+    @property
+    def cell_thresh(self):
+        """An element is dropped iff its 24-bit draw is below this."""
+        return _thresh(self.cell_prob)
+
+    @property
+    def active(self):
+        return bool(self.cell_thresh or self.erase_thresh)
+
+
+class MapNoise(object):
+    """Settings of the resident loader's localisation noise on the vector map and the target point.  shift (metres, [0, 64]) and
+    yaw_deg ([0, 45]): the lane set of a sample is rotated by yaw_deg * w and moved by shift * (w, w') with each w uniform in
+    [-1, 1); lane_drop: probability that a lane other than lane 0 (the query of the lane attention) is left out, the others
+    closing up; target_shift (metres, [0, 64]): the target point moves by target_shift * (w, w').  seed as in CameraJitter."""
+
+    def __init__(self, shift=0.0, yaw_deg=0.0, lane_drop=0.0, target_shift=0.0, seed=0):
+        self.shift, self.yaw_deg = _prob("MapNoise", "shift", shift, 64.0), _prob("MapNoise", "yaw_deg", yaw_deg, 45.0)
+        self.lane_drop, self.target_shift = _prob("MapNoise", "lane_drop", lane_drop), _prob("MapNoise", "target_shift", target_shift, 64.0)
+        self.seed = int(seed)
+
+    @property
+    def lane_thresh(self):
+        """Lane j >= 1 is dropped iff its 24-bit draw is below this."""
+        return _thresh(self.lane_drop)
+
+    @property
+    def yaw_rad(self):
+        """The largest rotation as the f32 the kernel multiplies: rounded once, here."""
+        return np.float32(self.yaw_deg * np.pi / 180.0)
+
+    @property
+    def lanes_active(self):
+        return bool(self.shift or self.yaw_deg or self.lane_thresh)
+
+    @property
+    def active(self):
+        return bool(self.lanes_active or self.target_shift)
+
+
+class Augment(object):
+    """What ResidentLoader(augment=...) takes when more than the camera is augmented: camera = CameraJitter or None, lidar =
+    LidarDropout or None, map = MapNoise or None.  A part that is None, or whose strengths are all zero, leaves its fields in the
+    plain gather launch."""
+
+    def __init__(self, camera=None, lidar=None, map=None):
+        for nm, v, cls in (("camera", camera, CameraJitter), ("lidar", lidar, LidarDropout), ("map", map, MapNoise)):
+            if v is not None and not isinstance(v, cls):
+                raise TypeError("Augment: %s takes a %s (or None), got %r" % (nm, cls.__name__, v))
+        self.camera, self.lidar, self.map = camera, lidar, map
 
 
 def _hash32(x):
@@ -493,12 +589,29 @@ def rng_u32(seed, step, stream, idx):
     return _hash32(((lo ^ salt) + ((hi * np.uint64(0x9E3779B1)) & np.uint64(_M32))) & np.uint64(_M32))
 
 
+def _sample_draws(seed, epoch, stream, sample_ids):
+    """int64 [len(sample_ids), 8]: k_j = mmfn_rng_u32(key of `stream`, id * 8 + j) >> 8."""
+    ids = np.asarray(sample_ids, dtype=np.int64).reshape(-1)
+    idx = ids[:, None].astype(np.uint64) * np.uint64(8) + np.arange(8, dtype=np.uint64)[None, :]
+    return (rng_u32(seed, epoch, stream, idx) >> np.uint64(8)).astype(np.int64)
+
+
 def jitter_draws(seed, epoch, sample_ids):
     """int64 [len(sample_ids), 8]: the eight 24-bit draws k_0..k_7 the jitter kernel makes for global sample ids in epoch `epoch`
     (k_j = mmfn_rng_u32(key, id * 8 + j) >> 8): brightness, contrast, saturation, erase or not, rectangle height, width, x, y."""
-    ids = np.asarray(sample_ids, dtype=np.int64).reshape(-1)
-    idx = ids[:, None].astype(np.uint64) * np.uint64(8) + np.arange(8, dtype=np.uint64)[None, :]
-    return (rng_u32(seed, epoch, RNG_STREAM_JITTER, idx) >> np.uint64(8)).astype(np.int64)
+    return _sample_draws(seed, epoch, RNG_STREAM_JITTER, sample_ids)
+
+
+def lidar_draws(seed, epoch, sample_ids):
+    """int64 [len(sample_ids), 8]: a sample's LiDAR draws (stream RNG_STREAM_LIDAR): k_0..k_2 reserved, then erase or not,
+    rectangle height, width, x, y - the layout of jitter_draws, so erase_rectangle reads both."""
+    return _sample_draws(seed, epoch, RNG_STREAM_LIDAR, sample_ids)
+
+
+def map_draws(seed, epoch, sample_ids):
+    """int64 [len(sample_ids), 8]: a sample's map draws (stream RNG_STREAM_MAP): shift x, shift y, yaw, target shift x, target
+    shift y; k_5..k_7 unused.  w_j = 2 * k_j * 2^-24 - 1."""
+    return _sample_draws(seed, epoch, RNG_STREAM_MAP, sample_ids)
 
 
 def erase_rectangle(draws, jitter, H, W):
@@ -532,6 +645,70 @@ def camera_jitter_reference(frames, gray_mean, draws, jitter):
             y0, x0, h, w = rect
             x[i, :, y0:y0 + h, x0:x0 + w] = m[i]
     return x
+
+
+def lidar_dropout_reference(frames, ids, aug, epoch):
+    """What mmfn_gather_augment writes for LiDAR frames [N, C, H, W] (f32 bits kept) whose samples have the global ids `ids` [N]
+    under aug = LidarDropout in epoch `epoch`: f32 [N, C, H, W], dropped elements and the erased rectangle +0.0."""
+    x = np.array(frames, dtype=np.float32)
+    N, C, H, W = x.shape
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    bits = x.view(np.uint32).reshape(N, -1)
+    if aug.cell_thresh:
+        idx = ids.astype(np.uint64)[:, None] * np.uint64(C * H * W) + np.arange(C * H * W, dtype=np.uint64)[None, :]   # wraps mod 2^64
+        bits[(rng_u32(aug.seed, epoch, RNG_STREAM_LIDAR_CELL, idx) >> np.uint64(8)) < np.uint64(aug.cell_thresh)] = 0
+    k = lidar_draws(aug.seed, epoch, ids)
+    for i in range(N):
+        rect = erase_rectangle(k[i], aug, H, W)
+        if rect is not None:
+            y0, x0, h, w = rect
+            x[i, :, y0:y0 + h, x0:x0 + w] = 0.0
+    return x
+
+
+def lane_keep_mask(ids, counts, aug, epoch):
+    """bool [N, max(counts)]: True where lane j < counts[b] of the sample with global id ids[b] stays under aug = MapNoise in
+    epoch `epoch` (lane 0 always; lane j >= 1 iff its draw mmfn_rng_u32(key_LANE, id * 65536 + j) >> 8 is not below lane_thresh);
+    False from counts[b] on."""
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    L = int(counts.max()) if counts.size else 0
+    j = np.arange(L, dtype=np.uint64)[None, :]
+    draw = rng_u32(aug.seed, epoch, RNG_STREAM_LANE, ids.astype(np.uint64)[:, None] * np.uint64(65536) + j) >> np.uint64(8)
+    keep = (draw >= np.uint64(aug.lane_thresh)) | (j == 0)
+    return keep & (np.arange(L)[None, :] < counts[:, None])
+
+
+def map_noise_reference(lanes, counts, target_point, ids, aug, epoch):
+    """What mmfn_gather_augment writes for the padded lane sets lanes [N, lmax, nodes, 5] with `counts` [N] stored lanes each (the
+    plain loader's lane / lane_num) and target points [N, 2], under aug = MapNoise: (lanes float64 [N, lmax, nodes, 5], counts
+    int64 [N], target points float64 [N, 2]).  The first min(count, lmax) lanes take part; kept lanes close up in stored order, the
+    rows after them are +0.0, counts lose the dropped lanes.  Nodes that are not all zero turn by yaw_rad * w_2 and move by
+    shift * (w_0, w_1), in float64; with shift = yaw_deg = 0 (target_shift = 0) values are copied, so their f32 bits survive."""
+    src = np.asarray(lanes)
+    N, lmax = src.shape[:2]
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    w = 2.0 * (map_draws(aug.seed, epoch, ids).astype(np.float64) / 16777216.0) - 1.0
+    shift, yaw, tshift = float(np.float32(aug.shift)), float(aug.yaw_rad), float(np.float32(aug.target_shift))
+    keep = lane_keep_mask(ids, np.minimum(counts, lmax), aug, epoch)
+    out = np.zeros(src.shape, dtype=np.float64)
+    out_counts = counts.copy()
+    for b in range(N):
+        rows = np.flatnonzero(keep[b])
+        out_counts[b] -= min(int(counts[b]), lmax) - len(rows)
+        x = src[b, rows].astype(np.float64)                               # [kept, nodes, 5]
+        if shift or yaw:
+            c, s_ = np.cos(yaw * w[b, 2]), np.sin(yaw * w[b, 2])
+            real = (x != 0.0).any(axis=-1)                                # an all-zero node is padding
+            xr = c * x[..., 0] - s_ * x[..., 1] + shift * w[b, 0]
+            yr = s_ * x[..., 0] + c * x[..., 1] + shift * w[b, 1]
+            x[..., 0], x[..., 1] = np.where(real, xr, x[..., 0]), np.where(real, yr, x[..., 1])
+        out[b, :len(rows)] = x
+    tp = np.array(target_point, dtype=np.float64).reshape(N, 2)
+    if tshift:
+        tp = tp + tshift * w[:, 3:5]
+    return out, out_counts, tp
 
 
 class ResidentFrames(object):
@@ -720,15 +897,52 @@ class ResidentFrames(object):
                     nm, str(t.dtype).replace("torch.", ""), list(shape), " kept as 4-bit codes" if nm + ".palette" in self.tensors else ""))
         return [self.tensors[nm] for nm in names]
 
-    def gather(self, index, rows, lane_bucket=None, jitter=None):
+    def lidar_frames(self):
+        """(the resident LiDAR tensors frame by frame, their palettes or None): [n, C * H * W] u8 / f32 each, or [n, C * H * W / 2]
+        codes with one f32 [16] palette per frame, after checking that the augmenting gather can take them: ValueError for a
+        LiDAR field that is not [C, H, W], or whose frames differ in shape, dtype or form."""
+        S = self.seq_len
+        names = self.plan_["arrays"][S:2 * S]
+        coded = [nm + ".palette" in self.tensors for nm in names]
+        for nm in names:
+            shape, t = self.shapes[nm], self.tensors[nm]
+            if len(shape) != 3 or shape != self.shapes[names[0]] or t.dtype not in (torch.uint8, torch.float32) \
+                    or t.dtype != self.tensors[names[0]].dtype or any(c != coded[0] for c in coded):
+                raise ValueError("LiDAR dropout needs [C, H, W] u8, f32 or 4-bit coded LiDAR frames, all of one form; field %s is %s %s%s" % (
+                    nm, str(t.dtype).replace("torch.", ""), list(shape), " kept as 4-bit codes" if nm + ".palette" in self.tensors else ""))
+        return [self.tensors[nm] for nm in names], ([self.tensors[nm + ".palette"] for nm in names] if coded[0] else None)
+
+    def lane_field(self):
+        """(the resident lane rows f32 [rows, nodes * 5], their prefix table) after checking that the augmenting gather can take
+        them: ValueError for a store without a lane field (variant 'img') or one that is not f32 [nodes, 5]."""
+        if self.variant == "img":
+            raise ValueError("MapNoise: shift, yaw_deg and lane_drop act on the lane set, which an 'img' store does not hold "
+                             "(target_shift works on every variant)")
+        nm = self.plan_["arrays"][2 * self.seq_len]
+        shape, t = self.shapes[nm], self.tensors[nm]
+        if len(shape) != 2 or shape[1] != 5 or t.dtype != torch.float32:
+            raise ValueError("map noise needs f32 lanes of [nodes, 5]; field %s is %s %s" % (nm, str(t.dtype).replace("torch.", ""), list(shape)))
+        return t, self.tensors[nm + ".row_off"]
+
+    def gather(self, index, rows, lane_bucket=None, jitter=None, augment=None):
         """(engine input dict, gt) of the batch whose resident rows are `rows` (host) = `index` (int64 device tensor, the same
         values): fresh tensors from the caching allocator and one gather launch on the current stream.  `jitter` = (CameraJitter,
         gray_mean f32 [n, S], state uint64 [2], sample_id int64 [n]), the last three on the device (ResidentLoader keeps them): the
-        camera field then goes through the jitter launch, every other field through the gather launch as before."""
+        camera field then goes through the jitter launch, every other field through the gather launch as before.
+        `augment` = {"sample_id": int64 [n], "camera": (CameraJitter, gray_mean, state), "lidar": (LidarDropout, state), "map":
+        (MapNoise, state)}, each part optional: the LiDAR frames, the lane set and the target point a part touches leave the gather
+        launch for one mmfn_gather_augment launch - at most three launches per batch.  ValueError for a lane-augmented batch of
+        more than 4096 lanes per sample."""
         from . import ops
         B, S, dev, T = len(rows), self.seq_len, self.device, self.tensors
         arrays = self.plan_["arrays"]
         fields = []
+        augment = augment or {}
+        if jitter is None and "camera" in augment:
+            jitter = tuple(augment["camera"]) + (augment["sample_id"],)
+        lidar, noise = augment.get("lidar"), augment.get("map")
+        move_lanes = noise is not None and noise[0].lanes_active
+        move_target = noise is not None and noise[0].target_shift != 0.0
 
         def frames(names, plain=True):   # frame s of sample b -> batch entry b * S + s, as MMFN._pack interleaves them
             shape = self.shapes[names[0]]
@@ -741,13 +955,14 @@ class ResidentFrames(object):
                                                palette=T.get(nm + ".palette")))
             return out
 
-        def dense(nm, shape):
+        def dense(nm, shape, plain=True):
             out = torch.empty((B,) + shape, dtype=torch.float32, device=dev)
-            fields.append(ops.gather_field(T[nm], out, row_elems=out[0].numel() if B else 0, palette=T.get(nm + ".palette")))
+            if plain:
+                fields.append(ops.gather_field(T[nm], out, row_elems=out[0].numel() if B else 0, palette=T.get(nm + ".palette")))
             return out
 
-        inp = {"image": frames(arrays[:S], plain=jitter is None), "lidar": frames(arrays[S:2 * S]), "target_point": dense("target_point", (2,)),
-               "velocity": dense("velocity", ())}
+        inp = {"image": frames(arrays[:S], plain=jitter is None), "lidar": frames(arrays[S:2 * S], plain=lidar is None),
+               "target_point": dense("target_point", (2,), plain=not move_target), "velocity": dense("velocity", ())}
         if self.variant == "img":
             inp["map"] = frames(arrays[2 * S:3 * S])
         else:
@@ -755,10 +970,13 @@ class ResidentFrames(object):
             lmax = int(self.lane_counts[rows].max()) if B else 0
             if lane_bucket and lane_bucket > 1 and lmax % lane_bucket:
                 lmax += lane_bucket - lmax % lane_bucket       # what trainer._bucket_lanes would append, as zeros of the same launch
+            if move_lanes and lmax > AUGMENT_MAX_LANES:
+                raise ValueError("a lane-augmented batch takes at most %d lanes per sample, this one has %d" % (AUGMENT_MAX_LANES, lmax))
             inp["lane"] = torch.empty((B, lmax) + self.shapes[nm], dtype=torch.float32, device=dev)
             inp["lane_num"] = torch.empty(B, dtype=torch.int32, device=dev)
-            fields.append(ops.gather_field(T[nm], inp["lane"], row_elems=T[nm].shape[1], row_off=T[nm + ".row_off"],
-                                           count_out=inp["lane_num"], lmax=lmax))
+            if not move_lanes:
+                fields.append(ops.gather_field(T[nm], inp["lane"], row_elems=T[nm].shape[1], row_off=T[nm + ".row_off"],
+                                               count_out=inp["lane_num"], lmax=lmax))
         if self.variant == "rad":
             inp["radar"] = dense(arrays[2 * S + 1], (RADAR_ROWS, 5))
             inp["radar_adj"] = dense(arrays[2 * S + 2], (RADAR_ROWS, RADAR_ROWS))
@@ -772,6 +990,21 @@ class ResidentFrames(object):
                                          brightness=aug.brightness, contrast=aug.contrast, saturation=aug.saturation,
                                          erase_thresh=aug.erase_thresh, erase_h=aug.erase_bounds(H), erase_w=aug.erase_bounds(W),
                                          sample_id=sample_id)
+            if lidar is not None or move_lanes or move_target:
+                parts = {}
+                if lidar is not None:
+                    aug, state = lidar
+                    srcs, palettes = self.lidar_frames()
+                    H, W = self.shapes[arrays[S]][1:]
+                    parts["lidar"] = dict(srcs=srcs, palettes=palettes, dst=inp["lidar"], state=state, cell_thresh=aug.cell_thresh,
+                                          erase_thresh=aug.erase_thresh, erase_h=aug.erase_bounds(H), erase_w=aug.erase_bounds(W))
+                if move_lanes:
+                    src, row_off = self.lane_field()
+                    parts["lanes"] = dict(src=src, row_off=row_off, dst=inp["lane"], count_out=inp["lane_num"],
+                                          lane_thresh=noise[0].lane_thresh, shift=noise[0].shift, yaw_rad=noise[0].yaw_rad)
+                if move_target:
+                    parts["target"] = dict(src=T["target_point"], dst=inp["target_point"], shift=noise[0].target_shift)
+                ops.gather_augment(index, self.n, sample_id=augment["sample_id"], map_state=noise[1] if noise is not None else None, **parts)
         return inp, gt
 
 
@@ -792,8 +1025,11 @@ class ResidentLoader(object):
     `augment` = CameraJitter(...) jitters the camera frames inside their gather (a second launch per batch, for that field alone):
     the draws depend on (augment.seed, this loader's epoch counter, global sample id) only, so a shard draws what the full store
     would.  The loader then holds the frames' gray means (f32 [n, S], computed once here), the {seed, epoch} state the kernel reads
-    and the sample ids, all on the device and none of them in the store.  None (the default) is the plain path, bit for bit; build
-    validation loaders without it.  PackedLoader and the pickle loaders are not augmented."""
+    and the sample ids, all on the device and none of them in the store.  `augment` = Augment(camera=, lidar=, map=) adds LiDAR
+    dropout, lane dropout and map noise (LidarDropout, MapNoise): the fields they touch go through a third launch, each part with
+    a state of its own; a part that is None or whose strengths are all zero stays in the plain launch, and Augment(camera=j) is
+    augment=j.  None (the default) is the plain path, bit for bit; build validation loaders without it.  PackedLoader and the
+    pickle loaders are not augmented."""
     device_resident = True
 
     def __init__(self, resident, batch_size, shuffle=False, sampler=None, seed=0, drop_last=False, lane_bucket=None, augment=None):
@@ -801,12 +1037,24 @@ class ResidentLoader(object):
         self.seed, self.drop_last, self.lane_bucket = seed, drop_last, lane_bucket
         self.epoch = 0
         self.augment = augment
-        if augment is not None:
-            if not isinstance(augment, CameraJitter):
-                raise TypeError("augment takes a CameraJitter (or None), got %r" % (augment,))
-            # what the jitter launch reads besides the store lives HERE: the store, its plan and its byte count stay as they are
+        if augment is None:
+            return
+        if not isinstance(augment, (CameraJitter, Augment)):
+            raise TypeError("augment takes a CameraJitter or an Augment (or None), got %r" % (augment,))
+        # what the augmenting launches read besides the store lives HERE: the store, its plan and its byte count stay as they are
+        state = lambda: torch.zeros(2, dtype=torch.int64, device=resident.device)      # {seed, epoch}, the kernel's uint64[2]
+        parts = Augment(camera=augment) if isinstance(augment, CameraJitter) else augment
+        if isinstance(augment, CameraJitter) or (parts.camera is not None and parts.camera.active):
             self.gray_mean = self._gray_mean(resident)
-            self.jitter_state = torch.zeros(2, dtype=torch.int64, device=resident.device)      # {seed, epoch}, the kernel's uint64[2]
+            self.jitter_state = state()
+        if parts.lidar is not None and parts.lidar.active:
+            resident.lidar_frames()
+            self.lidar_state = state()
+        if parts.map is not None and parts.map.active:
+            if parts.map.lanes_active:
+                resident.lane_field()
+            self.map_state = state()
+        if any(hasattr(self, nm) for nm in ("jitter_state", "lidar_state", "map_state")):
             self.sample_id = torch.from_numpy(np.ascontiguousarray(resident.indices, dtype=np.int64)).to(resident.device)
 
     @staticmethod
@@ -829,12 +1077,30 @@ class ResidentLoader(object):
         n = len(self.sampler) if self.sampler is not None else len(self.resident)
         return _num_batches(n, self.batch_size, self.drop_last)
 
+    def _states(self):
+        """Writes {seed, epoch} of every augmenting part and returns gather()'s keywords: the epoch counter that seeds the shuffle
+        also keys the draws."""
+        if self.augment is None:
+            return {}
+        put = lambda t, seed: t.copy_(torch.tensor([_as_i64(seed), _as_i64(self.epoch)], dtype=torch.int64))
+        if isinstance(self.augment, CameraJitter):
+            put(self.jitter_state, self.augment.seed)
+            return {"jitter": (self.augment, self.gray_mean, self.jitter_state, self.sample_id)}
+        parts = {}
+        if hasattr(self, "jitter_state"):
+            parts["camera"] = (self.augment.camera, self.gray_mean, put(self.jitter_state, self.augment.camera.seed))
+        if hasattr(self, "lidar_state"):
+            parts["lidar"] = (self.augment.lidar, put(self.lidar_state, self.augment.lidar.seed))
+        if hasattr(self, "map_state"):
+            parts["map"] = (self.augment.map, put(self.map_state, self.augment.map.seed))
+        if not parts:
+            return {}
+        parts["sample_id"] = self.sample_id
+        return {"augment": parts}
+
     def __iter__(self):
         order = self._order()
-        jitter = None
-        if self.augment is not None:     # the epoch counter that seeds the shuffle also keys the draws
-            self.jitter_state.copy_(torch.tensor([_as_i64(self.augment.seed), _as_i64(self.epoch)], dtype=torch.int64))
-            jitter = (self.augment, self.gray_mean, self.jitter_state, self.sample_id)
+        extra = self._states()
         self.epoch += 1
         res = self.resident
         rows = res.rows_of(order) if self.sampler is not None else np.asarray(order, dtype=np.int64)
@@ -842,10 +1108,7 @@ class ResidentLoader(object):
         pos = 0
         for chunk in _chunks(order, self.batch_size, self.drop_last):
             b = len(chunk)
-            if jitter is None:
-                yield res.gather(index[pos:pos + b], rows[pos:pos + b], self.lane_bucket)
-            else:
-                yield res.gather(index[pos:pos + b], rows[pos:pos + b], self.lane_bucket, jitter=jitter)
+            yield res.gather(index[pos:pos + b], rows[pos:pos + b], self.lane_bucket, **extra)
             pos += b
 
 

@@ -1368,6 +1368,63 @@ def gather_camera_jitter(srcs, dst, gray_mean, state, index, n, brightness=0.0, 
     return dst
 
 
+def gather_augment(index, n, sample_id=None, lidar=None, lanes=None, target=None, map_state=None):
+    """The bird's-eye-view fields of one batch gathered AND augmented in one launch (csrc/resident.hip, mmfn_gather_augment); each
+    of the three parts is a dict or None:
+      lidar  = dict(srcs = 1..4 tensors [n, C * H * W] u8 / f32 or [n, C * H * W / 2] u8 codes, palettes = None or one f32 [16] per
+               frame (coded), dst = f32 [B * S, C, H, W], state = int64 [2] {seed, epoch}, cell_thresh, erase_thresh, erase_h, erase_w)
+      lanes  = dict(src = f32 [rows, nodes, 5], row_off = int64 [n + 1], dst = f32 [B, lmax, nodes, 5], count_out = int32 [B] or
+               None, lane_thresh, shift, yaw_rad)
+      target = dict(src = f32 [n, 2], dst = f32 [B, 2], shift)
+    map_state: int64 [2] {seed, epoch} of lanes and target; index: int64 device [B]; sample_id: int64 device [n] or None (= the
+    row).  Thresholds are round(prob * 2^24).  Capturable: index, sample_id, the states and row_off are read by the kernel."""
+    if index.dtype != torch.int64 or not index.is_contiguous():
+        raise ValueError("gather_augment: index must be a contiguous int64 tensor")
+    d = _lib.GatherAugmentDesc()
+    d.sample_id, d.map_state = ptr(sample_id), ptr(map_state)
+    if lidar is not None:
+        srcs, dst, pals = lidar["srcs"], lidar["dst"], lidar.get("palettes")
+        if not 1 <= len(srcs) <= _lib.AUGMENT_MAX_FRAMES:
+            raise ValueError("gather_augment: 1..%d LiDAR frames per sample, got %d" % (_lib.AUGMENT_MAX_FRAMES, len(srcs)))
+        if dst.dim() != 4 or dst.dtype != torch.float32 or not dst.is_contiguous():
+            raise ValueError("gather_augment: the LiDAR dst must be a contiguous f32 [B * S, C, H, W] tensor")
+        coded = pals is not None
+        if coded and (len(pals) != len(srcs) or any(t is not None and t.dtype != torch.uint8 for t in srcs)):
+            raise ValueError("gather_augment: a coded LiDAR field is u8 codes with one palette per frame")
+        row = dst[0].numel() if dst.shape[0] else int(torch.Size(dst.shape[1:]).numel())
+        for s, t in enumerate(srcs):
+            if t is not None and (t.dtype != srcs[0].dtype or t.dtype not in (torch.uint8, torch.float32) or not t.is_contiguous()
+                                  or (t.shape[0] and t[0].numel() * (2 if coded else 1) != row)):
+                raise ValueError("gather_augment: every LiDAR source is a contiguous [n, C * H * W] u8 / f32 tensor (or [n, C * H * W / 2] "
+                                 "codes) of one dtype")
+            d.lidar_src[s] = ptr(t)
+            if coded:
+                d.lidar_palette[s] = ptr(pals[s])
+        d.parts |= _lib.AUGMENT_LIDAR
+        d.lidar_dst, d.lidar_state = ptr(dst), ptr(lidar["state"])
+        d.n_frames, d.C, d.H, d.W = len(srcs), dst.shape[1], dst.shape[2], dst.shape[3]
+        d.src_type = _lib.GATHER_PAL4 if coded else (_lib.GATHER_U8 if srcs[0] is not None and srcs[0].dtype == torch.uint8 else _lib.GATHER_F32)
+        d.cell_thresh, d.erase_thresh = int(lidar.get("cell_thresh", 0)), int(lidar.get("erase_thresh", 0))
+        (d.erase_h_min, d.erase_h_max), (d.erase_w_min, d.erase_w_max) = ((int(v) for v in lidar.get(k, (1, 1))) for k in ("erase_h", "erase_w"))
+    if lanes is not None:
+        src, dst = lanes["src"], lanes["dst"]
+        if dst.dim() != 4 or dst.shape[3] != 5 or dst.dtype != torch.float32 or not dst.is_contiguous():
+            raise ValueError("gather_augment: the lane dst must be a contiguous f32 [B, lmax, nodes, 5] tensor")
+        if src is not None and (src.dtype != torch.float32 or not src.is_contiguous() or (src.shape[0] and src[0].numel() != dst.shape[2] * 5)):
+            raise ValueError("gather_augment: the lane source is a contiguous f32 [rows, nodes * 5] tensor")
+        if dst.shape[1] > _lib.AUGMENT_MAX_LANES:
+            raise ValueError("gather_augment: a lane-augmented launch takes at most %d lanes per sample, got lmax = %d" % (
+                _lib.AUGMENT_MAX_LANES, dst.shape[1]))
+        d.parts |= _lib.AUGMENT_LANES
+        d.lane_src, d.lane_row_off, d.lane_dst, d.lane_count_out = ptr(src), ptr(lanes["row_off"]), ptr(dst), ptr(lanes.get("count_out"))
+        d.lane_nodes, d.lmax, d.lane_thresh = dst.shape[2], dst.shape[1], int(lanes.get("lane_thresh", 0))
+        d.shift, d.yaw_rad = float(lanes.get("shift", 0.0)), float(lanes.get("yaw_rad", 0.0))
+    if target is not None:
+        d.parts |= _lib.AUGMENT_TARGET
+        d.target_src, d.target_dst, d.target_shift = ptr(target["src"]), ptr(target["dst"]), float(target.get("shift", 0.0))
+    _call("mmfn_gather_augment", ctypes.byref(d), ptr(index), index.numel(), int(n), stream())
+
+
 def polyline_pool_fwd(y, out, arg, R, V, H, last):
     _call("mmfn_polyline_pool_fwd_f32", ptr(y), ptr(out), ptr(arg), R, V, H, 1 if last else 0, stream())
     return out
