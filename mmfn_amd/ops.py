@@ -569,8 +569,25 @@ def conv2d_fwd_bn_stats(x, w, stride, pad, out, mean, rstd, running_mean, runnin
     else:
         assert x_bn is None
         conv2d_fwd(x, w, stride, pad, out=out, keep_v=keep_v, keep_u=keep_u, u_ready=u_ready)
-    M = out.numel() // out.shape[-1]
-    bn_train_stats(out.view(M, out.shape[-1]), mean, rstd, running_mean, running_var, nbt, eps, momentum)
+    C = out.shape[-1]
+    M = out.numel() // C
+    cq = C // 4
+    if C % 4 or cq > 256 or 256 % cq == 0:
+        bn_train_stats(out.view(M, C), mean, rstd, running_mean, running_var, nbt, eps, momentum)
+        return out
+    # The statistics kernels lane a block as 256 / (C / 4) rows x C / 4 float4 columns and refuse a width whose quad count does not
+    # divide 256 (e.g. 96 channels, which the Winograd path accepts).  No layer of the model has one; such an output is copied into
+    # the next width the kernel takes, zero columns appended, and the statistics of the real columns are copied back.
+    Cp = 4 << (cq - 1).bit_length()
+    xp = torch.zeros(M, Cp, dtype=out.dtype, device=out.device)
+    xp[:, :C].copy_(out.view(M, C))
+    meanp, rstdp = (torch.empty(Cp, dtype=torch.float32, device=out.device) for _ in range(2))
+    rmp, rvp = (torch.zeros(Cp, dtype=torch.float32, device=out.device) for _ in range(2))
+    rmp[:C].copy_(running_mean)
+    rvp[:C].copy_(running_var)
+    bn_train_stats(xp, meanp, rstdp, rmp, rvp, nbt, eps, momentum)
+    for dst, src in ((mean, meanp), (rstd, rstdp), (running_mean, rmp), (running_var, rvp)):
+        dst.copy_(src[:C])
     return out
 
 
