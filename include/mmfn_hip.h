@@ -548,6 +548,24 @@ int mmfn_adamw_groups_f32(float* p, const float* g, float* m, float* v, int64_t 
                           int n_groups, const int64_t* step, int variant, const float* coef, float* avg, const int64_t* n_averaged,
                           const float* ema_w, int avg_mode, const int32_t* ok, void* stream);
 
+/* Per-tensor step counts (torch.optim.AdamW's state[p]["step"]: a parameter's count advances only on the steps it has a gradient
+ * for, so a tensor unfrozen late starts its bias correction at 1).  Tensors that took part in exactly the same step launches share
+ * a step CLASS with one int64 counter in class_steps [n_classes] (device memory, 8-byte aligned).  The byte a float4 reads in
+ * row_of (one per float4, mandatory) selects a ROW = (hyper group, step class): rows is a HOST array [n_rows][2] of (group, class),
+ * 1 <= n_rows <= MMFN_ADAMW_MAX_ROWS, every group < n_groups and every class < n_classes; the map travels as a kernel argument, so
+ * it is fixed at launch (and in a captured hipGraph) while the counters stay in device memory.  Each row's scalars are formed from
+ * hyper[group] and class_steps[class] exactly as mmfn_adamw_groups_f32 forms a group's from *step: a float4 of row (g, c) gets the
+ * bits that entry point gives it with step = class_steps[c].  Byte MMFN_ADAMW_FROZEN keeps its meaning (MASK is implied; any byte
+ * >= n_rows is treated alike).  variant: COEF / AVG / GUARD as above, without the MASK bit.  Any NULL or misaligned pointer the
+ * launch would read, or a count out of range: MMFN_EINVAL. */
+#define MMFN_ADAMW_MAX_ROWS 254
+int mmfn_adamw_rows_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* row_of, const float* hyper,
+                        int n_groups, const int32_t* rows, int n_rows, const int64_t* class_steps, int n_classes, int variant,
+                        const float* coef, float* avg, const int64_t* n_averaged, const float* ema_w, int avg_mode, const int32_t* ok,
+                        void* stream);
+/* class_steps[c] += 1 for every c < n_classes with active[c] != 0 (device bytes); ok (may be NULL): only when *ok (the guard) */
+int mmfn_class_steps_advance(int64_t* class_steps, const uint8_t* active, int n_classes, const int32_t* ok, void* stream);
+
 /* ---- gradient accumulation and global-norm clipping over the flat gradient buffer ------------------------------ */
 #define MMFN_ACCUM_NONE 0 /* read g only (needs partials) */
 #define MMFN_ACCUM_ADD 1  /* acc += g */

@@ -1,7 +1,8 @@
 // Fused AdamW over the flat parameter buffer (run_steps/phase2_train_net.py:110,256:
 // torch.optim.AdamW defaults lr 1e-4, betas (0.9, 0.999), eps 1e-8, weight_decay 1e-2).
 // HBM-bound: 28 B/param (read p,g,m,v; write p,m,v) in one pass with 16-byte accesses.
-// The step count lives in device memory so the launch is hipGraph-replayable.
+// The step count lives in device memory so the launch is hipGraph-replayable.  Per-tensor step counts (a tensor unfrozen late
+// starts its bias correction at 1, as torch.optim.AdamW's state[p]["step"]): one counter per step class, adamw_rows_kernel below.
 #include <algorithm>
 
 #include "common.h"
@@ -238,6 +239,132 @@ extern "C" int mmfn_adamw_groups_f32(float* p, const float* g, float* m, float* 
     return MMFN_EINVAL;
   hipLaunchKernelGGL(kAdamwGroups[variant], dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, group_of, hyper,
                      n_groups, step, with_coef ? coef : nullptr, a, guard ? ok : nullptr);
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- grouped AdamW with per-tensor step counts ----------------------------------------------------------------------------------
+// torch.optim.AdamW keeps state[p]["step"] per parameter and advances it only on the steps where the parameter has a gradient, so a
+// tensor unfrozen late starts its bias correction at 1.  Tensors that took part in exactly the same step launches form a step
+// CLASS with one int64 counter in class_steps (device memory).  The byte a float4 reads selects a ROW = (hyper group, step class):
+// the rows' scalars are formed at block start from hyper[group of row] and class_steps[class of row], with the arithmetic of
+// adamw_groups_kernel expression for expression, and the element loop is that kernel's MASK instance.  The same bytes move: no
+// per-tensor id stream, no extra HBM traffic.  The row map travels as a kernel argument, checked on the host by the entry point.
+namespace {
+struct AdamwRowMap {
+  uint16_t cls[MMFN_ADAMW_MAX_ROWS];
+  uint8_t group[MMFN_ADAMW_MAX_ROWS];
+};
+
+template <bool COEF, bool AVG, bool GUARD>
+__global__ __launch_bounds__(256) void adamw_rows_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                         float* __restrict__ v, int64_t n, const uint8_t* __restrict__ row_of,
+                                                         const float* __restrict__ hyper, AdamwRowMap rows, int n_rows,
+                                                         const int64_t* __restrict__ class_steps, const float* __restrict__ coef,
+                                                         AvgArgs avg, const int32_t* __restrict__ ok) {
+  if (GUARD && !*ok) return;   // uniform over the grid: no barrier is left behind
+  __shared__ GroupScalars gs[MMFN_ADAMW_MAX_ROWS];   // 254 * 32 B = 8128 B
+  if ((int)threadIdx.x < n_rows) {
+    const float* h = hyper + rows.group[threadIdx.x] * 8;
+    const double t = (double)class_steps[rows.cls[threadIdx.x]];
+    const double lr = (double)h[0], beta1 = (double)h[1], beta2 = (double)h[2];
+    GroupScalars s;
+    s.step_size = (float)(lr / (1.0 - pow(beta1, t)));
+    s.decay = (float)(1.0 - lr * (double)h[4]);
+    s.bc2_sqrt = (float)sqrt(1.0 - pow(beta2, t));
+    s.beta1 = h[1]; s.beta2 = h[2]; s.eps = h[3]; s.grad_scale = COEF ? h[5] * *coef : h[5]; s.pad = 0.f;
+    gs[threadIdx.x] = s;
+  }
+  __syncthreads();
+  const int64_t n4 = (n + 3) >> 2;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    const int r = row_of[i];
+    if (r >= n_rows) {   // MMFN_ADAMW_FROZEN (a byte that names no row is treated alike: it never indexes past the rows in LDS)
+      if (AVG) {
+        const f32x4 pf = *reinterpret_cast<const f32x4*>(p + i * 4);
+        f32x4 out = pf;
+        if (*avg.n_averaged != 0) out = lerp4(*reinterpret_cast<const f32x4*>(avg.avg + i * 4), pf, avg_weight(avg));
+        *reinterpret_cast<f32x4*>(avg.avg + i * 4) = out;
+      }
+      continue;
+    }
+    const GroupScalars s = gs[r];
+    f32x4 pv = *reinterpret_cast<f32x4*>(p + i * 4);
+    f32x4 gv = *reinterpret_cast<const f32x4*>(g + i * 4);
+    f32x4 mv = *reinterpret_cast<f32x4*>(m + i * 4);
+    f32x4 vv = *reinterpret_cast<f32x4*>(v + i * 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float gg = gv[e] * s.grad_scale;
+      pv[e] *= s.decay;
+      mv[e] = mv[e] + (gg - mv[e]) * (1.0f - s.beta1);
+      vv[e] = vv[e] * s.beta2 + (1.0f - s.beta2) * gg * gg;
+      const float denom = sqrtf(vv[e]) / s.bc2_sqrt + s.eps;
+      pv[e] = pv[e] - s.step_size * (mv[e] / denom);
+    }
+    *reinterpret_cast<f32x4*>(p + i * 4) = pv;
+    *reinterpret_cast<f32x4*>(m + i * 4) = mv;
+    *reinterpret_cast<f32x4*>(v + i * 4) = vv;
+    if (AVG) {   // (the empty asm: see adamw_groups_kernel)
+      f32x4 out = pv;
+      asm volatile("" : "+v"(out));
+      pv = out;
+      if (*avg.n_averaged != 0) out = lerp4(*reinterpret_cast<const f32x4*>(avg.avg + i * 4), pv, avg_weight(avg));
+      *reinterpret_cast<f32x4*>(avg.avg + i * 4) = out;
+    }
+  }
+}
+
+using AdamwRowsKernel = decltype(&adamw_rows_kernel<false, false, false>);
+const AdamwRowsKernel kAdamwRows[8] = {   // by variant; nullptr: GUARD without COEF, which is not built
+    adamw_rows_kernel<false, false, false>, adamw_rows_kernel<true, false, false>, adamw_rows_kernel<false, true, false>,
+    adamw_rows_kernel<true, true, false>,   nullptr,                                adamw_rows_kernel<true, false, true>,
+    nullptr,                                adamw_rows_kernel<true, true, true>};
+
+// class_steps[c] += 1 for every class whose byte in `active` is set: one thread per class, plain stores
+template <bool GUARD>
+__global__ __launch_bounds__(256) void class_steps_advance_kernel(int64_t* __restrict__ class_steps, const uint8_t* __restrict__ active,
+                                                                  int n_classes, const int32_t* __restrict__ ok) {
+  if (GUARD && !*ok) return;
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < n_classes && active[c]) class_steps[c] = class_steps[c] + 1;
+}
+}  // namespace
+
+extern "C" int mmfn_adamw_rows_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* row_of, const float* hyper,
+                                   int n_groups, const int32_t* rows, int n_rows, const int64_t* class_steps, int n_classes,
+                                   int variant, const float* coef, float* avg, const int64_t* n_averaged, const float* ema_w,
+                                   int avg_mode, const int32_t* ok, void* stream) {
+  if (n <= 0) return 0;
+  if (variant < 0 || variant >= 8 || !kAdamwRows[variant]) return MMFN_EINVAL;
+  const bool with_coef = variant & MMFN_ADAMW_COEF, with_avg = variant & MMFN_ADAMW_AVG, guard = variant & MMFN_ADAMW_GUARD;
+  const AvgArgs a = with_avg ? AvgArgs{avg, n_averaged, ema_w, avg_mode} : AvgArgs{};
+  if (!p || !g || !m || !v || !row_of || !rows || n_rows < 1 || n_rows > MMFN_ADAMW_MAX_ROWS || n_classes < 1 || n_classes > 65536 ||
+      ((uintptr_t)class_steps & 7) || !adamw_args_ok(p, g, m, v, n, hyper, n_groups, class_steps) || (with_coef && !coef) ||
+      (with_avg && !avg_args_ok(a)) || (guard && !flag_ok(ok)))
+    return MMFN_EINVAL;
+  AdamwRowMap map{};
+  for (int r = 0; r < n_rows; ++r) {   // rows: HOST memory, [n_rows][2] = (group, class), every entry inside its table
+    const int32_t grp = rows[2 * r], cls = rows[2 * r + 1];
+    if (grp < 0 || grp >= n_groups || cls < 0 || cls >= n_classes) return MMFN_EINVAL;
+    map.group[r] = (uint8_t)grp;
+    map.cls[r] = (uint16_t)cls;
+  }
+  hipLaunchKernelGGL(kAdamwRows[variant], dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, row_of, hyper, map,
+                     n_rows, class_steps, with_coef ? coef : nullptr, a, guard ? ok : nullptr);
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mmfn_class_steps_advance(int64_t* class_steps, const uint8_t* active, int n_classes, const int32_t* ok, void* stream) {
+  if (!class_steps || ((uintptr_t)class_steps & 7) || !active || n_classes < 1 || n_classes > 65536 || ((uintptr_t)ok & 3))
+    return MMFN_EINVAL;
+  const hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((n_classes + 255) / 256);
+  if (ok)
+    hipLaunchKernelGGL(class_steps_advance_kernel<true>, grid, dim3(256), 0, st, class_steps, active, n_classes, ok);
+  else
+    hipLaunchKernelGGL(class_steps_advance_kernel<false>, grid, dim3(256), 0, st, class_steps, active, n_classes, ok);
   MMFN_LAUNCH_CHECK();
   return 0;
 }

@@ -1483,6 +1483,16 @@ class Engine(object):
         self._filled = set()        # ... and the groups zeroed so far in the running backward
         self._mask_table = None     # (optimizer group table it was built from, effective table with 255 over frozen float4s)
         self.never_stepped = None   # names frozen at every optimizer step so far (None: no step yet): FusedAdamW.state_dict
+        # per-tensor AdamW step counts (params.StepClasses): one device counter per step class, read by the AdamW launch with
+        # step classes once a class that steps no longer carries step_count; until then step_count serves everybody
+        self.classes = layout.step_classes
+        n_trained = max(len(self.classes.names), 1)   # (a class holds at least one tensor)
+        self._class_steps = torch.zeros(n_trained, dtype=torch.int64, device=dev)
+        self._class_active = torch.ones(n_trained, dtype=torch.uint8, device=dev)
+        self._row_table = None      # (optimizer group table, classes.epoch, device row table, host rows)
+        self._class_index = None    # (classes.epoch, device class index per trained tensor): tensor_steps
+        if not self.classes.stepped and any(self.classes.values):   # counts loaded before the engine existed
+            self.set_tensor_steps(self.classes.host_steps(), step_count=max(self.classes.values))
         self.n_lanes = int(os.environ.get("MMFN_BRANCH_LANES", "3"))
         self.offload_wgrad = True   # transformer weight / bias gradients on the side stream (worth 3.9 ms per step)
 
@@ -1535,6 +1545,7 @@ class Engine(object):
         L.frozen = frozen
         self._mask_table = None
         self._fill_tabs = {}
+        self._install_classes(self.classes.install(frozen))
         if not frozen:
             self._fz, self._plan = frozenset(), None
             return
@@ -1606,6 +1617,71 @@ class Engine(object):
                 raise RuntimeError("the optimizer's group table changed inside a hipGraph capture")
             self._mask_table = (ids, self.layout.group_table(self.frozen, ids).to(self.device))
         return self._mask_table[1]
+
+    # ------------------------------------------------------------------ per-tensor step counts (params.StepClasses)
+    def _install_classes(self, splits=()):
+        """The device side of a change of the step classes (new flags, set_tensor_steps), outside a capture: a class split off
+        another one gets a copy of its counter, every class that still carries step_count gets that value (its slot is not
+        advanced while the shared counter serves all classes that step), and the active bytes follow the flags."""
+        C = self.classes
+        dev = self.device
+        if splits:
+            new, src = (torch.tensor(x, dtype=torch.int64, device=dev) for x in zip(*splits))
+            self._class_steps[new] = self._class_steps[src]
+        synced = [c for c in range(C.n_classes) if C.synced[c]]
+        if synced:
+            self._class_steps[torch.tensor(synced, dtype=torch.int64, device=dev)] = self.step_count
+        active = torch.zeros(self._class_active.numel(), dtype=torch.uint8)
+        active[:C.n_classes] = torch.tensor(C.active, dtype=torch.uint8)
+        self._class_active.copy_(active)
+        self._row_table = None
+
+    def _rows(self, n_groups):
+        """(device row table, host rows) of the AdamW launch with step classes for the installed flags and the optimizer's groups
+        (one row of hyper-parameters: everything is group 0, as in _group_table).  Built outside a capture."""
+        ids = self.opt_group_of if n_groups > 1 else None
+        C = self.classes
+        if self._row_table is None or self._row_table[0] is not ids or self._row_table[1] != C.epoch:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the optimizer's group table or the step classes changed inside a hipGraph capture")
+            tab, rows = C.row_table(self.layout, self.frozen, ids)
+            self._row_table = (ids, C.epoch, tab.to(self.device), rows)
+        return self._row_table[2], self._row_table[3]
+
+    def _advance_steps(self, ok=None):
+        """step_count += 1, and every active class counter with it once the classes have their own (behind the guard's flag)."""
+        ops.step_advance(self.step_count, ok=ok)
+        if not self.classes.uniform():
+            ops.class_steps_advance(self._class_steps, self._class_active, self.classes.n_classes, ok=ok)
+
+    def tensor_steps(self):
+        """int64 CPU tensor: the AdamW step count of every trained tensor, in layout order (classes.names) - what
+        torch.optim.AdamW holds in state[p]["step"].  One small device-to-host copy."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("tensor_steps() inside a hipGraph capture")
+        C = self.classes
+        if self._class_index is None or self._class_index[0] != (C.epoch, tuple(C.synced)):
+            self._class_index = ((C.epoch, tuple(C.synced)), torch.tensor(C.cls, dtype=torch.int64, device=self.device),
+                                 torch.tensor(C.synced, dtype=torch.bool, device=self.device))
+        _, cls, synced = self._class_index
+        per_class = torch.where(synced, self.step_count, self._class_steps[:C.n_classes])
+        return per_class[cls].cpu()
+
+    def set_tensor_steps(self, steps, step_count=None):
+        """Set every trained tensor's step count (layout order, as tensor_steps() returns them); the classes are rebuilt from the
+        distinct values.  step_count: the count of optimizer steps taken (None: it stays what it is)."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("set_tensor_steps() inside a hipGraph capture")
+        steps = [int(s) for s in (steps.tolist() if isinstance(steps, torch.Tensor) else steps)]
+        if step_count is None:
+            step_count = int(self.step_count.item())
+        C = self.classes
+        C.set_steps(steps, step_count)
+        self.step_count.fill_(int(step_count))
+        self._class_steps.zero_()
+        self._class_steps[:C.n_classes] = torch.tensor(C.values, dtype=torch.int64, device=self.device)
+        self._install_classes(C.install(self.frozen))
+        self._class_index = None
 
     # ------------------------------------------------------------------ LayerNorm folded into the Linear behind it (fp32 path)
     def ln_fold_now(self, training):
@@ -2025,7 +2101,7 @@ class Engine(object):
         groups = self.hyper_rows(lr, betas, eps, weight_decay, grad_scale, groups)
         self.set_hyper(groups)
         self.module.weights_changed()
-        ops.step_advance(self.step_count)
+        self._advance_steps()
         self._adamw(len(groups))
 
     # ------------------------------------------------------------------ weight average (mmfn_amd.averaging)
@@ -2048,7 +2124,12 @@ class Engine(object):
         the non-finite guard's flag, every one of them behind it."""
         L, a = self.layout, self.average
         avg = None if a is None else (a.module._layout.params, a.n_averaged, a.ema_weight, a.mode_code)
-        if self.frozen:
+        if not self.classes.uniform():
+            # a tensor that steps has a count of its own: the instance whose bias corrections follow the step classes
+            row_of, rows = self._rows(n_groups)
+            ops.adamw_rows(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self._class_steps, self.classes.n_classes, self.opt_hyper,
+                           n_groups, row_of, rows, n=L.tail, coef=coef, avg=avg, ok=ok)
+        elif self.frozen:
             # the masked instance: frozen float4s keep parameter, moments and decay untouched (the average still follows them)
             ops.adamw_groups(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self.step_count, self.opt_hyper, n_groups,
                              group_of=self._group_table(n_groups), n=L.tail, coef=coef, avg=avg, ok=ok, mask=True)
@@ -2056,6 +2137,7 @@ class Engine(object):
             ops.adamw_groups(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self.step_count, self.opt_hyper, n_groups,
                              group_of=self.opt_group_of if n_groups > 1 else None, n=L.tail, coef=coef, avg=avg, ok=ok)
         self.never_stepped = self.frozen if self.never_stepped is None else (self.never_stepped & self.frozen)
+        self.classes.launched()
         if a is not None:
             a.update_buffers(self.module, ok=ok)
             ops.step_advance(a.n_averaged, ok=ok)
@@ -2282,7 +2364,7 @@ class Engine(object):
             raise RuntimeError("the non-finite guard decides on the gradient norm: its optimizer step is the clipped one")
         self.module.weights_changed()
         if guard is None:
-            ops.step_advance(self.step_count)
+            self._advance_steps()
         coef = ok = None
         if clip:
             nm = self._norm_state()
@@ -2307,7 +2389,7 @@ class Engine(object):
             ok, skipped = (None, None) if guard is None else (guard["ok"], guard["skipped"])
             ops.grad_norm_finalize(part, self.opt_hyper[0, 5:6], self.opt_hyper[0, 6:7], out[0:1], coef, ok=ok, skipped=skipped)
             if guard is not None:
-                ops.step_advance(self.step_count, ok=ok)
+                self._advance_steps(ok=ok)
                 ops.copy_if(L.buffers_flat, guard["buffers"], ok, when=False)    # skipped: the group's BatchNorm updates go
                 ops.copy_if(L.counters_flat, guard["counters"], ok, when=False)
         self._adamw(n_groups, coef=coef, ok=ok)

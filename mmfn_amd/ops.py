@@ -1210,6 +1210,39 @@ def adamw_groups(p, g, m, v, step, hyper, n_groups, group_of=None, n=None, coef=
           ptr(coef), ptr(a), ptr(n_averaged), ptr(ema_weight), int(mode), ptr(ok), stream())
 
 
+ADAMW_MAX_ROWS = 254   # mirror include/mmfn_hip.h
+
+
+def adamw_rows(p, g, m, v, class_steps, n_classes, hyper, n_groups, row_of, rows, n=None, coef=None, avg=None, ok=None):
+    """AdamW with per-tensor step counts: row_of (uint8, one byte per float4, ADAMW_FROZEN over frozen float4s) selects a row of
+    `rows` (a CPU int32 tensor [n_rows, 2] of (hyper group, step class)); a row's bias corrections come from class_steps[class]
+    (int64, device).  coef / avg / ok as in adamw_groups; frozen float4s as in its masked launch."""
+    n = p.numel() if n is None else n
+    if row_of is None or row_of.dtype != torch.uint8 or row_of.numel() * 4 < n:
+        raise ValueError("the AdamW launch with step classes needs a uint8 row table with one byte per float4 of the range")
+    if rows.device.type != "cpu" or rows.dtype != torch.int32 or rows.dim() != 2 or rows.shape[1] != 2 or not rows.is_contiguous():
+        raise ValueError("rows is a contiguous CPU int32 tensor [n_rows, 2] of (group, class)")
+    if not 1 <= rows.shape[0] <= ADAMW_MAX_ROWS:
+        raise ValueError("%d (group, step class) rows: the AdamW launch holds at most %d" % (rows.shape[0], ADAMW_MAX_ROWS))
+    if class_steps.dtype != torch.int64 or class_steps.numel() < n_classes:
+        raise ValueError("class_steps holds %d %s counters, the launch reads %d int64" % (class_steps.numel(), class_steps.dtype, n_classes))
+    a, n_averaged, ema_weight, mode = (None, None, None, 0) if avg is None else avg
+    if a is not None and a.numel() < n:
+        raise ValueError("average holds %d floats, the step covers %d" % (a.numel(), n))
+    if ok is not None and coef is None:
+        raise ValueError("the guarded AdamW launch is the coefficient instance: pass coef")
+    variant = sum(bit for bit, arg in ((ADAMW_COEF, coef), (ADAMW_AVG, avg), (ADAMW_GUARD, ok)) if arg is not None)
+    _call("mmfn_adamw_rows_f32", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(row_of), ptr(hyper), n_groups, rows.data_ptr(), rows.shape[0],
+          ptr(class_steps), n_classes, variant, ptr(coef), ptr(a), ptr(n_averaged), ptr(ema_weight), int(mode), ptr(ok), stream())
+
+
+def class_steps_advance(class_steps, active, n_classes, ok=None):
+    """class_steps[c] += 1 for every class c < n_classes whose byte in `active` (uint8, device) is set; ok: the guard's flag."""
+    if class_steps.dtype != torch.int64 or active.dtype != torch.uint8 or min(class_steps.numel(), active.numel()) < n_classes:
+        raise ValueError("class_steps (int64) and active (uint8) hold one entry per class")
+    _call("mmfn_class_steps_advance", ptr(class_steps), ptr(active), n_classes, ptr(ok), stream())
+
+
 ACCUM_NONE, ACCUM_ADD, ACCUM_FOLD = 0, 1, 2   # mirror include/mmfn_hip.h
 
 

@@ -4,7 +4,8 @@ The reference trains with `optim.AdamW(model.parameters(), lr=args.lr)` (run_ste
 and saves `optimizer.state_dict()` next to the weights (`best_optim.pth`, `recent_optim.pth`, :209,216).
 FusedAdamW drives mmfn_adamw_groups_f32 (one launch over all 104.8 M trained parameters, csrc/optim.hip) and reads /
 writes that same state-dict layout: parameter ids in group order (one group: `model.parameters()` order), per-id
-`step`, `exp_avg`, `exp_avg_sq` in checkpoint shapes (OIHW for convolutions), and no entry for the
+`step` (every tensor's own count: a tensor unfrozen late is behind the others, Engine.tensor_steps), `exp_avg`,
+`exp_avg_sq` in checkpoint shapes (OIHW for convolutions), and no entry for the
 parameters that never receive a gradient (vec/rad: the raster-map stem + layer1) -
 exactly what torch's optimizer holds after a reference run.
 
@@ -144,18 +145,26 @@ class FusedAdamW(object):
                 out.append((name, view(L.exp_avg), view(L.exp_avg_sq)))
         return out
 
+    def _engine(self):
+        """The engine of a module on a GPU; None for a module built on the CPU (its counts then live in the layout alone)."""
+        return self.model._engine_for() if self.model._layout.device.type == "cuda" else None
+
+    def tensor_steps(self):
+        """{name: AdamW step count} of every trained tensor: torch.optim.AdamW's state[p]["step"] (Engine.tensor_steps)."""
+        L, eng = self.model._layout, self._engine()
+        steps = eng.tensor_steps().tolist() if eng is not None else L.step_classes.host_steps()
+        return dict(zip(L.step_classes.names, steps))
+
     def state_dict(self):
         L = self.model._layout
-        eng = self.model._engine_for()
-        steps = int(eng.step_count.item())
+        steps = self.tensor_steps()
         state = {}
-        never = eng.never_stepped or ()   # frozen at every optimizer step so far: torch holds no state for them either
-        if steps > 0:
-            for idx, (name, m, v) in enumerate(self._moment_views()):
-                if name in L.unused or name in never:
-                    continue
-                state[idx] = {"step": torch.tensor(float(steps)), "exp_avg": m.clone().contiguous(),
-                              "exp_avg_sq": v.clone().contiguous()}
+        # a tensor that never took a step (frozen at every optimizer step so far, or no step yet): torch holds no state for it either
+        for idx, (name, m, v) in enumerate(self._moment_views()):
+            if name in L.unused or steps[name] == 0:
+                continue
+            state[idx] = {"step": torch.tensor(float(steps[name])), "exp_avg": m.clone().contiguous(),
+                          "exp_avg_sq": v.clone().contiguous()}
         groups = []
         start = 0
         for g, names in zip(self.param_groups, self._group_names):
@@ -167,8 +176,10 @@ class FusedAdamW(object):
         return {"state": state, "param_groups": groups}
 
     def load_state_dict(self, sd):
+        """Per-parameter `step` values may differ (a torch run that unfroze tensors late): every tensor keeps its own count.  An
+        id without an entry has count 0 and zero moments; a trained tensor outside this optimizer's groups likewise."""
         L = self.model._layout
-        eng = self.model._engine_for()
+        eng = self._engine()
         if len(sd["param_groups"]) != len(self.param_groups):
             raise ValueError("optimizer state has %d parameter groups, this optimizer %d" % (len(sd["param_groups"]), len(self.param_groups)))
         for mine, names, theirs in zip(self.param_groups, self._group_names, sd["param_groups"]):
@@ -177,7 +188,7 @@ class FusedAdamW(object):
             for k in _HYPER:
                 if k in theirs:
                     mine[k] = tuple(theirs[k]) if k == "betas" else theirs[k]
-        steps = set()
+        steps = {}
         absent = set()
         L.exp_avg.zero_()
         L.exp_avg_sq.zero_()
@@ -188,8 +199,11 @@ class FusedAdamW(object):
                 continue
             m.copy_(st["exp_avg"])
             v.copy_(st["exp_avg_sq"])
-            steps.add(int(float(st["step"])))
-        if len(steps) > 1:
-            raise ValueError("per-parameter step counts differ (%s): one shared counter is kept on the device" % sorted(steps))
+            steps[name] = int(float(st["step"]))
+        vec = [steps.get(n, 0) for n in L.step_classes.names]
+        top = max(vec) if vec else 0
+        if eng is None:
+            L.step_classes.set_steps(vec, top)
+            return
         eng.never_stepped = frozenset(absent) if steps else None
-        eng.step_count.fill_(steps.pop() if steps else 0)
+        eng.set_tensor_steps(vec, step_count=top)   # (step_count: the count of optimizer steps, the largest per-tensor one)

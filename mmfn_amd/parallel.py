@@ -88,6 +88,11 @@ class DataParallel(object):
         if L.device.type == "cuda":  # (the CPU unit tests exercise the bucket logic without an engine)
             eng = self.module._engine_for()
             self.dist.broadcast(eng.step_count, src)
+            # ... and the per-tensor step counts beside it (tensors unfrozen late are behind step_count): every rank rebuilds
+            # its step classes from the same vector
+            steps = eng.tensor_steps().to(L.device)
+            self.dist.broadcast(steps, src)
+            eng.set_tensor_steps(steps.cpu())
             self.dist.broadcast(eng.rng_state, src)
             eng.rng_state[0] += self.dist.get_rank()  # per-rank dropout streams
             if eng.average is not None:
@@ -370,6 +375,9 @@ class GraphedStep(object):
         self.average = eng.average   # folded into the captured AdamW launch (or not): a replay must find the same attachment
         if eng.trainable_mask() != self.mask:
             raise RuntimeError("requires_grad flags changed during the warm-up steps of a capture")
+        # per-tensor step counts: the captured AdamW launch is the shared-counter one or the one with step classes, for the
+        # partition of this moment (Engine.set_tensor_steps changes it without touching a flag)
+        self.class_epoch = eng.classes.epoch
         try:
             rec.capture(body)
         finally:
@@ -402,6 +410,9 @@ class GraphedStep(object):
         if eng.trainable_mask() != self.mask:
             raise RuntimeError("this step was captured with other requires_grad flags (%d parameter(s) differ): capture the step again"
                                % sum(a != b for a, b in zip(eng._mask_flags, self.mask)))
+        if self.variant != "micro" and eng.classes.epoch != self.class_epoch:
+            raise RuntimeError("this step was captured for other per-tensor step counts (Engine.set_tensor_steps, a loaded optimizer "
+                               "state): capture the step again")
         if self.variant != "micro" and eng.nonfinite_guard != self.guard:
             raise RuntimeError("this step was captured with the non-finite guard %s; the engine now has it %s: capture the step again"
                                % (("armed", "disarmed") if self.guard else ("disarmed", "armed")))

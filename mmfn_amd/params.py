@@ -209,6 +209,7 @@ class FlatLayout(object):
             self.group_ranges[key] = (min(b, o), max(e, o + (k + 3) // 4 * 4))
         self.unused = unused
         self.frozen = frozenset()   # trained-range names whose requires_grad is False, as the engine last read them (Engine.trainable_mask)
+        self.step_classes = StepClasses([n for n in self.offsets if n not in unused])   # per-tensor AdamW step counts
         self.device = None
         self.params = self.grads = self.exp_avg = self.exp_avg_sq = None
         self.buffers_flat = None
@@ -392,6 +393,126 @@ class FlatLayout(object):
             b, e = self.span(n)
             gid[b // 4:e // 4] = 255
         return gid
+
+
+class StepClasses(object):
+    """Host bookkeeping of the per-tensor AdamW step counts (torch.optim.AdamW's state[p]["step"]).
+
+    A step class is a set of trained tensors that took part in exactly the same optimizer-step launches, so they share one count.
+    The host knows the partition - the requires_grad flags only change between launches - but not the counts: the non-finite
+    guard decides on the device whether a launched step is taken.  Per class the host keeps
+      active   none of its tensors is frozen under the flags last installed (a class never mixes frozen and trainable tensors);
+      synced   the class took part in every step launch so far, so its count IS the engine's step count;
+      values   its count as set_steps() last set it (exact only until the next step launch: `stepped`).
+    While every active class is synced (uniform()), one shared counter gives every trained tensor its own bias correction and the
+    engine launches what it always launched; the per-class counters on the device are needed only after that.
+    `epoch` grows whenever the partition, the active set or uniform() changes: what a captured step was recorded for."""
+    MAX_ROWS = 254
+
+    def __init__(self, names):
+        self.names = list(names)
+        self.cls = [0] * len(self.names)
+        self.n_classes = 1
+        self.active, self.synced, self.values = [True], [True], [0]
+        self.stepped = False
+        self.epoch = 0
+
+    def _key(self):
+        return tuple(self.cls), tuple(self.active), self.uniform()
+
+    def install(self, frozen):
+        """New requires_grad flags (`frozen`: the frozen names): a class whose tensors no longer share a flag splits, its frozen
+        tensors form a new class with a copy of the count.  Returns [(new class, class it was split from)]."""
+        before = self._key()
+        members = {}
+        for i, n in enumerate(self.names):
+            members.setdefault(self.cls[i], ([], []))[1 if n in frozen else 0].append(i)
+        splits = []
+        for c in sorted(members):
+            live, cold = members[c]
+            if live and cold:
+                new = self.n_classes
+                self.n_classes += 1
+                for i in cold:
+                    self.cls[i] = new
+                self.active[c] = True
+                self.active.append(False)
+                self.synced.append(self.synced[c])
+                self.values.append(self.values[c])
+                splits.append((new, c))
+            else:
+                self.active[c] = bool(live)
+        if self._key() != before:
+            self.epoch += 1
+        return splits
+
+    def launched(self):
+        """An optimizer step was launched (or captured) under the installed flags: the classes that sit it out leave the shared
+        count behind."""
+        self.stepped = True
+        for c in range(self.n_classes):
+            if not self.active[c]:
+                self.synced[c] = False
+
+    def uniform(self):
+        """Every class that steps carries the engine's step count: the shared counter serves all of them."""
+        return all(s for s, a in zip(self.synced, self.active) if a)
+
+    def set_steps(self, steps, step_count=None):
+        """Rebuild the classes from one count per trained tensor (layout order): one class per distinct value, the largest
+        first.  step_count: the engine's count of optimizer steps (default: the largest value).  Everything is active afterwards
+        until install() says otherwise."""
+        steps = [int(s) for s in steps]
+        if len(steps) != len(self.names):
+            raise ValueError("%d step counts for %d trained tensors" % (len(steps), len(self.names)))
+        if any(s < 0 for s in steps):
+            raise ValueError("a step count is negative")
+        before = self._key()
+        distinct = sorted(set(steps), reverse=True) or [0]
+        top = distinct[0] if step_count is None else int(step_count)
+        where = {s: c for c, s in enumerate(distinct)}
+        self.cls = [where[s] for s in steps]
+        self.n_classes = len(distinct)
+        self.values = list(distinct)
+        self.synced = [s == top for s in distinct]
+        self.active = [True] * len(distinct)
+        self.stepped = False
+        if self._key() != before:
+            self.epoch += 1
+
+    def host_steps(self):
+        """One count per trained tensor from the values set_steps() left (a module that never stepped on a device)."""
+        if self.stepped:
+            raise RuntimeError("optimizer steps ran since the counts were set: they live on the device (Engine.tensor_steps)")
+        return [self.values[c] for c in self.cls]
+
+    def members(self):
+        """[names] per class."""
+        out = [[] for _ in range(self.n_classes)]
+        for n, c in zip(self.names, self.cls):
+            out[c].append(n)
+        return out
+
+    def row_table(self, layout, frozen, group_of=None):
+        """The row table of the AdamW launch with step classes: (one byte per float4 of the flat buffer - the row of the tensor
+        it belongs to, 255 (MMFN_ADAMW_FROZEN) over frozen and never-trained float4s - as a CPU uint8 tensor, rows as a CPU int32
+        tensor [n_rows, 2] of (optimizer group, step class)).  group_of: the optimizer's group id per float4 (uint8) or None =
+        one group.  Rows are numbered in layout order of their first tensor."""
+        gid = None if group_of is None else group_of.detach().to("cpu")
+        tab = torch.full((layout.total // 4,), 255, dtype=torch.uint8)
+        rows, spans = {}, []
+        for n, c in zip(self.names, self.cls):
+            if n in frozen:
+                continue
+            b, e = layout.span(n)
+            key = (0 if gid is None else int(gid[b // 4]), c)
+            spans.append((b, e, rows.setdefault(key, len(rows))))
+        if len(rows) > self.MAX_ROWS:
+            raise ValueError("%d (optimizer group, step class) rows: the AdamW launch holds at most %d - fewer distinct per-tensor "
+                             "step counts or fewer parameter groups" % (len(rows), self.MAX_ROWS))
+        for b, e, r in spans:
+            tab[b // 4:e // 4] = r
+        return tab, torch.tensor(sorted(rows, key=rows.get), dtype=torch.int32).view(-1, 2)
 
 
 def default_unused(variant):

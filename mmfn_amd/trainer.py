@@ -224,6 +224,8 @@ class Trainer(object):
                 sig = sig + ("guard",)
             if eng.frozen:   # (frozen parameters: the pruned backward and the masked AdamW are captures of their own, per set of flags)
                 sig = sig + (mask,)
+            if eng.classes.epoch and final:   # (per-tensor step counts: the AdamW launch follows the step classes of the moment)
+                sig = sig + (("step classes", eng.classes.epoch),)
             state = self._static_steps.pop(sig, None)
             if state == "seen":
                 try:
@@ -483,7 +485,7 @@ def _plain_state_dict(model):
 
 def fit(model, optimizer, train_loader, val_loader, config, logdir, epochs, val_every=1, save_every=1, dp=None, rank=0,
         on_log=None, dist=None, accum_steps=1, clip_grad_norm=None, average=None, average_every="step", average_start_epoch=0,
-        skip_nonfinite=False):
+        skip_nonfinite=False, unfreeze_at=None):
     """The epoch loop of phase2_train_net.py:307-322: train every epoch; rank 0 validates every `val_every`
     epochs and saves every `save_every`.  Data parallel: pass `dp` (a parallel.DataParallel), or just the initialised
     torch.distributed module as `dist` - the transport is then chosen by parallel.connect: the C-ABI RCCL communicator when it
@@ -496,13 +498,26 @@ def fit(model, optimizer, train_loader, val_loader, config, logdir, epochs, val_
     validates average.module into trainer.val_loss_average and saves averaged_model.pth / best_averaged_model.pth; every rank
     keeps its own copy, in lock step because the parameters are (DataParallel.broadcast_average after a resume).
     skip_nonfinite: Trainer.train's option, every epoch (a skipped step is skipped on every rank: the norm is taken after the
-    gradient reduction)."""
+    gradient reduction).
+    unfreeze_at = {epoch: [name prefixes]}: gradual unfreezing.  The caller freezes what starts frozen (model.freeze(...)); at the
+    start of that epoch every rank calls model.unfreeze(*prefixes) (a prefix that matches nothing raises, here, before the first
+    step), and a resumed run applies the entries of the epochs up to the one it resumes into before its first step.  The tensors
+    unfrozen late start their AdamW bias correction at step 1, as torch.optim.AdamW's per-parameter counts do (Engine.tensor_steps),
+    and the optimizer checkpoint carries those counts."""
     if average_every not in ("step", "epoch"):
         raise ValueError("average_every must be 'step' or 'epoch', got %r" % (average_every,))
     if dp is None and dist is not None and dist.get_world_size() > 1:
         from .parallel import connect
         dp, _ = connect(model, dist)
         rank = dist.get_rank()
+    schedule = {}
+    have = [n for n, _ in model.named_parameters()]
+    for at, prefixes in (unfreeze_at or {}).items():
+        prefixes = [prefixes] if isinstance(prefixes, str) else list(prefixes)
+        for pre in prefixes:
+            if not any(n.startswith(pre) for n in have):
+                raise ValueError("unfreeze_at[%r]: no parameter name starts with %r" % (at, pre))
+        schedule[int(at)] = prefixes
     trainer = Trainer(model._layout.device, logdir)
     if rank == 0:
         trainer.resume(model, optimizer, average=average)
@@ -511,7 +526,12 @@ def fit(model, optimizer, train_loader, val_loader, config, logdir, epochs, val_
         sync_resume_state(trainer, optimizer, dp.dist)  # epoch / iteration counters, loss history, lr & co
         if average is not None:
             dp.broadcast_average(average)
+    for at in sorted(schedule):   # a resumed run: what the epochs before this one unfroze (after sync_resume_state: on every rank)
+        if at < trainer.cur_epoch:
+            model.unfreeze(*schedule[at])
     for epoch in range(trainer.cur_epoch, epochs):
+        if epoch in schedule:
+            model.unfreeze(*schedule[epoch])
         sampler = getattr(train_loader, "sampler", None)
         if hasattr(sampler, "set_epoch"):
             sampler.set_epoch(epoch)
