@@ -708,6 +708,66 @@ int mmfn_sizeof_camera_jitter_desc(void);
 /* d: HOST memory, copied into the launch (by value); n = samples in the store */
 int mmfn_gather_camera_jitter(const mmfn_camera_jitter_desc* d, const int64_t* index, int B, int64_t n, void* stream);
 
+/* ---- camera sensor degradation inside the gather (data.ResidentLoader(augment=data.Augment(degrade=data.CameraDegrade(...)))) --
+ * mmfn_gather_camera_jitter with three more stages between the colour blends and the erased rectangle: a hue shift, a Gaussian
+ * blur and additive Gaussian noise.  This launch takes the place of the jitter launch for the camera field; the jitter's members,
+ * draws and state keep their meaning, and its descriptor and entry point are untouched.
+ * Draws, integers only.  id as in the jitter.  key_D = mmfn_rng_key(degrade_state, 0x4447) (MMFN_RNG_STREAM_DEGRADE):
+ *   k_j = mmfn_rng_u32(key_D, id * 8 + j) >> 8, u_j = k_j * 2^-24: k_0 hue, k_1 blur or not, k_2 sigma, k_3 noise or not, k_4 noise
+ *   std, k_5..k_7 reserved.  All frames of a sample share them.  key_N = mmfn_rng_key(degrade_state, 0x504E)
+ *   (MMFN_RNG_STREAM_PIXEL_NOISE): element e = (c * H + y) * W + x of frame s draws n_0 = mmfn_rng_u32(key_N, 2 q) >> 8 and
+ *   n_1 = mmfn_rng_u32(key_N, 2 q + 1) >> 8 with q = (id * n_frames + s) * 3 H W + e in wrapping 64-bit arithmetic: the noise
+ *   differs from frame to frame of a sample.
+ * Arithmetic, fp32 per pixel on the 0..255 image, in this fixed order:
+ *   1. the jitter's contrast, brightness and saturation blends, as above.
+ *   2. hue, skipped when hue == 0 (no round trip touches the bits).  torchvision's _rgb2hsv / _hsv2rgb without the scale:
+ *        M = max(r, g, b), m = min(r, g, b), c = M - m, gray = (M == m);  s = c / (gray ? 1 : M);  i = 1 / (gray ? 1 : c);
+ *        rc = (M - r) i, gc = (M - g) i, bc = (M - b) i;
+ *        h6 = bc - gc if M == r, else 2 + rc - bc if M == g, else 4 + gc - rc;
+ *        h = fmaf(h6, 1/6, hue * (2 u_0 - 1));  h = h - floor(h);  f = 6 h - floor(6 h), sector = floor(6 h) mod 6;
+ *        p = clamp(M (1 - s)), q = clamp(M (1 - s f)), t = clamp(M (1 - s (1 - f)));
+ *        (r, g, b) = (M,t,p) (q,M,p) (p,M,t) (p,q,M) (t,p,M) (M,p,q) for sector 0..5.
+ *   3. blur, iff k_1 < blur_thresh.  sigma = fmaf(sigma_hi - sigma_lo, u_2, sigma_lo); taps w_d = expf(-d^2 / (2 sigma^2)) for
+ *        |d| <= R = blur_radius, divided by their sum w_0 + 2 (w_1 + ... + w_R); the rows are filtered first, then the columns:
+ *        out = fmaf(w_d, x[-d] + x[+d], ...) over d = 1..R on top of w_0 x[0].  Outside the frame the pixel mirrored at the
+ *        border without repeating it (index -1 -> 1, n -> n - 2: torch's pad(mode="reflect")).  The neighbours are the values
+ *        after stages 1 and 2.  The result is not clamped: it is a convex combination of values in [0, 255].
+ *   4. noise, iff k_3 < noise_thresh.  std = fmaf(std_hi - std_lo, u_4, std_lo); u1 = (n_0 + 1) * 2^-24, u2 = n_1 * 2^-24;
+ *        x = clamp(fmaf(std, sqrtf(-2 logf(u1)) * cosf(6.2831855f * u2), x)) with the precise library functions.
+ *   5. the jitter's erased rectangle: exactly the stored frame's gray mean.
+ *   hue 0 and both thresholds 0 give the bits of mmfn_gather_camera_jitter.
+ * A blurred sample goes through LDS tiles (csrc/resident.hip), an unblurred one through the jitter's pointwise path: the choice
+ * is the sample's, so the result depends on (seeds, epoch, id) alone.  Any H, W and alignment are accepted.
+ * MMFN_EINVAL, nothing launched: everything mmfn_gather_camera_jitter refuses; degrade_state NULL or not 8-byte aligned; hue
+ * outside [0, 0.5] or NaN; blur_thresh or noise_thresh > 2^24; blur_radius outside 0..MMFN_DEGRADE_MAX_RADIUS; while
+ * blur_thresh > 0: min(H, W) <= blur_radius, or sigma bounds outside 0 < lo <= hi <= 8/3 or NaN; while noise_thresh > 0: std
+ * bounds outside 0 <= lo <= hi <= 64 or NaN. */
+#define MMFN_DEGRADE_MAX_RADIUS 8
+typedef struct mmfn_camera_degrade_desc {
+  const void* src[MMFN_JITTER_MAX_FRAMES]; /* as in mmfn_camera_jitter_desc, down to erase_w_max */
+  float* dst;
+  const float* gray_mean;
+  const int64_t* sample_id;
+  const uint64_t* state;          /* DEVICE [2] = {seed, epoch} of the jitter's draws */
+  const uint64_t* degrade_state;  /* DEVICE [2] = {seed, epoch} of the draws above */
+  int32_t n_frames, src_type, H, W;
+  float brightness, contrast, saturation;
+  uint32_t erase_thresh;
+  int32_t erase_h_min, erase_h_max, erase_w_min, erase_w_max;
+  float hue;                                   /* in [0, 0.5]; 0 = the stage is skipped */
+  uint32_t blur_thresh;                        /* blur iff draw 1 < blur_thresh; round(prob * 2^24), 0 = never */
+  float blur_sigma_lo, blur_sigma_hi;          /* 0 < lo <= hi <= 8/3; ignored when blur_thresh == 0 */
+  int32_t blur_radius;                         /* R: 0..8, below min(H, W) while blur_thresh > 0 */
+  uint32_t noise_thresh;                       /* noise iff draw 3 < noise_thresh */
+  float noise_std_lo, noise_std_hi;            /* 0 <= lo <= hi <= 64, in the image's 0..255 units; ignored when noise_thresh == 0 */
+} mmfn_camera_degrade_desc;
+int mmfn_sizeof_camera_degrade_desc(void);
+/* rows and columns of the tile a workgroup blurs: for tests that want a frame of several tiles and a ragged rest */
+int mmfn_camera_degrade_tile_h(void);
+int mmfn_camera_degrade_tile_w(void);
+/* d: HOST memory, copied into the launch (by value); n = samples in the store */
+int mmfn_gather_camera_degrade(const mmfn_camera_degrade_desc* d, const int64_t* index, int B, int64_t n, void* stream);
+
 /* ---- LiDAR dropout, lane dropout and map noise inside the gather (data.ResidentLoader(augment=data.Augment(...))) -----------
  * The bird's-eye-view inputs of a batch, gathered by sample index as mmfn_gather_batch gathers them and augmented in the same
  * pass; `parts` says which of the three fields the launch carries (MMFN_AUGMENT_LIDAR | _LANES | _TARGET), the others' members

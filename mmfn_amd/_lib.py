@@ -101,6 +101,20 @@ class CameraJitterDesc(ctypes.Structure):
                 ("erase_h_min", _i32), ("erase_h_max", _i32), ("erase_w_min", _i32), ("erase_w_max", _i32)]
 
 
+DEGRADE_MAX_RADIUS = 8
+
+
+class CameraDegradeDesc(ctypes.Structure):
+    """mmfn_camera_degrade_desc (include/mmfn_hip.h): the jitter's launch with hue, Gaussian blur and sensor noise."""
+    _fields_ = [("src", _vp * JITTER_MAX_FRAMES), ("dst", _vp), ("gray_mean", _vp), ("sample_id", _vp), ("state", _vp),
+                ("degrade_state", _vp),
+                ("n_frames", _i32), ("src_type", _i32), ("H", _i32), ("W", _i32),
+                ("brightness", _f32), ("contrast", _f32), ("saturation", _f32), ("erase_thresh", ctypes.c_uint32),
+                ("erase_h_min", _i32), ("erase_h_max", _i32), ("erase_w_min", _i32), ("erase_w_max", _i32),
+                ("hue", _f32), ("blur_thresh", ctypes.c_uint32), ("blur_sigma_lo", _f32), ("blur_sigma_hi", _f32),
+                ("blur_radius", _i32), ("noise_thresh", ctypes.c_uint32), ("noise_std_lo", _f32), ("noise_std_hi", _f32)]
+
+
 AUGMENT_MAX_FRAMES, AUGMENT_MAX_LANES = 4, 4096
 AUGMENT_LIDAR, AUGMENT_LANES, AUGMENT_TARGET = 1, 2, 4
 
@@ -185,6 +199,8 @@ def lib():
             raise MMFNLibraryError("mmfn_gather_table layout mismatch between C and ctypes")
         if handle.mmfn_sizeof_camera_jitter_desc() != ctypes.sizeof(CameraJitterDesc):
             raise MMFNLibraryError("mmfn_camera_jitter_desc layout mismatch between C and ctypes")
+        if handle.mmfn_sizeof_camera_degrade_desc() != ctypes.sizeof(CameraDegradeDesc):
+            raise MMFNLibraryError("mmfn_camera_degrade_desc layout mismatch between C and ctypes")
         if handle.mmfn_sizeof_gather_augment_desc() != ctypes.sizeof(GatherAugmentDesc):
             raise MMFNLibraryError("mmfn_gather_augment_desc layout mismatch between C and ctypes")
         _lib = handle

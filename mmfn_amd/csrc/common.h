@@ -115,6 +115,10 @@ __device__ __forceinline__ uint64_t mmfn_rng_key(const uint64_t* state, uint32_t
 #define MMFN_RNG_STREAM_LIDAR_CELL 0x4C43u
 #define MMFN_RNG_STREAM_MAP 0x4D50u
 #define MMFN_RNG_STREAM_LANE 0x4C4Eu
+// streams of the resident loader's camera degradation (a sample's eight draws; two draws per element for the sensor noise):
+// mmfn_gather_camera_degrade, with a {seed, epoch} state of its own beside the jitter's
+#define MMFN_RNG_STREAM_DEGRADE 0x4447u
+#define MMFN_RNG_STREAM_PIXEL_NOISE 0x504Eu
 // keep-mask scale: 0 if dropped, 1/(1-p) if kept
 __device__ __forceinline__ float mmfn_dropout_scale(uint64_t key, uint64_t idx, float p, float inv_keep) {
   float u = (float)(mmfn_rng_u32(key, idx) >> 8) * (1.0f / 16777216.0f);

@@ -2,7 +2,8 @@
 // index - what PackedFrames.batch (np.take into pinned memory), the host->device copy and the u8 -> f32 widening of stage_batch do
 // in three steps on two processors.  Values are only moved (and u8 widened, which is exact): no arithmetic - except in the second
 // entry point at the end of the file, which gathers the camera field alone and colour-jitters it on the way, and in the third, which
-// gathers the LiDAR frames, the lane set and the target point and drops cells and lanes and moves the map on the way.
+// gathers the LiDAR frames, the lane set and the target point and drops cells and lanes and moves the map on the way, and in the
+// fourth, which is the second with a hue shift, a Gaussian blur (the one neighbourhood operation here: LDS tiles) and sensor noise.
 //   dense field   dst[b] = f32(src[index[b]])
 //   coded field   dst[b] = palette[4-bit codes of src[index[b]]]: a few-valued float field kept at half a byte per element
 //   ragged field  rows [off[i], off[i+1]) of the concatenated source -> dst[b, :count]; rows count..Lmax-1 = +0.0; count -> int32
@@ -629,7 +630,360 @@ __global__ __launch_bounds__(NT) void gather_augment_kernel(const mmfn_gather_au
   else
     lidar_piece<float, 4>(f, reinterpret_cast<const float*>(D.lidar_src[s]) + i * row, d, lo, hi, piece == 0, head, vec_ok);
 }
+
+// ---- camera degradation inside the gather (mmfn_gather_camera_degrade; draws and formulas: include/mmfn_hip.h) -------------------
+// The jitter launch with a hue shift, a Gaussian blur and sensor noise between the blends and the erased rectangle.  Whether a
+// sample is blurred is its own draw, the same in every lane of a workgroup, so a workgroup branches once:
+//   unblurred  the jitter's pointwise path (2048 consecutive pixels of one frame, four pixels per access), hue and noise in
+//              registers between the blends and the rectangle: no halo, no LDS traffic, no barrier.
+//   blurred    a BLUR_TH x BLUR_TW tile of one frame.  The tile plus an R-wide halo of all three planes is loaded element by
+//              element (consecutive lanes on consecutive pixels of a row: the halo's start is not aligned to anything), mirrored
+//              at the frame's border, blended and hue-shifted on the way into LDS - hue needs R, G and B of a pixel together,
+//              and the filter must see the neighbours' shifted values.  A lane has the loads of four pixels in flight: with one
+//              pixel at a time (a wave per row) the launch measured 73.4 us at B = 32 with every sample blurred, this way
+//              50.3 us (profiles/resident_degrade_bench.txt).  Then per plane: rows filtered out of that image into a second LDS
+//              buffer (a lane per column, taps d and -d paired: R + 1 multiplies), columns filtered out of it four pixels per
+//              lane (16-byte LDS reads), noise, rectangle, and one 16-byte store where the four pixels are inside the frame and
+//              the address allows, element stores otherwise.
+// Tile: 32 x 64 pixels.  Image (32 + 16) x (64 + 16) x 3 planes = 45 KB at the largest radius 8, plus ONE plane of row-filtered
+// values 48 x 64 = 12 KB (reused by the three planes, two barriers each): 57 KB, so two workgroups share a compute unit's 160 KB
+// with room to spare, and the halo costs 1.9 x the tile's own loads and blends.  (16 x 64 would fit four workgroups but load
+// 2.5 x; 64 x 64 loads 1.6 x but is alone on its compute unit.)  Rows of both buffers are read along x by consecutive lanes: no
+// bank conflicts.  The LDS is dynamic, so a launch whose blur probability is 0 asks for none and keeps the jitter's occupancy;
+// a launch that may blur gives it to every workgroup, blurred or not.
+// The taps are worked out by lanes 0..R (one expf each) and normalised by every lane from LDS in one fixed order; the frame's
+// other scalars come from scalar loads as in the jitter.
+constexpr int BLUR_TH = 32, BLUR_TW = 64, BLUR_RMAX = MMFN_DEGRADE_MAX_RADIUS;
+constexpr int BLUR_IN_H = BLUR_TH + 2 * BLUR_RMAX, BLUR_IN_W = BLUR_TW + 2 * BLUR_RMAX;
+constexpr int BLUR_PLANE = BLUR_IN_H * BLUR_IN_W;                    // floats of one plane's image
+constexpr int BLUR_MID = BLUR_IN_H * BLUR_TW;                        // floats of the row-filtered plane
+constexpr int BLUR_LOADS = 4;                                        // pixels a lane has in flight while the image is loaded
+constexpr size_t BLUR_LDS_BYTES = (size_t)(3 * BLUR_PLANE + BLUR_MID + 16) * sizeof(float);   // (+ the taps)
+
+struct DegradeFrame {
+  JitterFrame j;
+  int32_t hue, noise;          // 0: the stage is off for this launch / this sample
+  float shift;                 // hue shift, in turns
+  float noise_std;
+  uint64_t noise_key, noise_base;   // key of the element draws; (id * S + s) * 3 H W
+};
+
+__device__ __forceinline__ void hue_pixel(float shift, float& r, float& g, float& b) {
+  const float mx = fmaxf(r, fmaxf(g, b)), mn = fminf(r, fminf(g, b));
+  const float c = mx - mn;
+  const bool gray = mx == mn;
+  const float s = c / (gray ? 1.0f : mx);
+  const float inv = 1.0f / (gray ? 1.0f : c);
+  const float rc = (mx - r) * inv, gc = (mx - g) * inv, bc = (mx - b) * inv;
+  const float h6 = mx == r ? bc - gc : (mx == g ? 2.0f + rc - bc : 4.0f + gc - rc);
+  float h = fmaf(h6, 1.0f / 6.0f, shift);
+  h -= floorf(h);
+  const float hs = h * 6.0f, fl = floorf(hs), f = hs - fl;
+  int sector = (int)fl;
+  if (sector >= 6) sector -= 6;                    // (h rounded up to 1)
+  const float p = clamp255(mx * (1.0f - s)), q = clamp255(mx * (1.0f - s * f)), t = clamp255(mx * (1.0f - s * (1.0f - f)));
+  r = sector == 0 || sector == 5 ? mx : (sector == 1 ? q : (sector == 4 ? t : p));
+  g = sector == 1 || sector == 2 ? mx : (sector == 0 ? t : (sector == 3 ? q : p));
+  b = sector == 3 || sector == 4 ? mx : (sector == 2 ? t : (sector == 5 ? q : p));
+}
+
+// element e of the frame (e = (c * H + y) * W + x), value v
+__device__ __forceinline__ float degrade_noise(const DegradeFrame& F, float v, uint64_t e) {
+  const uint64_t q = F.noise_base + e;
+  const uint32_t n0 = mmfn_rng_u32(F.noise_key, 2 * q) >> 8, n1 = mmfn_rng_u32(F.noise_key, 2 * q + 1) >> 8;
+  const float u1 = (float)(n0 + 1u) * (1.0f / 16777216.0f), u2 = (float)n1 * (1.0f / 16777216.0f);
+  return clamp255(fmaf(F.noise_std, sqrtf(-2.0f * logf(u1)) * cosf(6.2831855f * u2), v));
+}
+
+// one pixel of the pointwise path: j = its offset in the plane, inside = it lies in the erased rectangle
+__device__ __forceinline__ void degrade_pixel(const DegradeFrame& F, float& r, float& g, float& b, int64_t j, int64_t HW, bool inside) {
+  jitter_pixel<false>(F.j, r, g, b, 0, 0);
+  if (F.hue) hue_pixel(F.shift, r, g, b);
+  if (F.noise) {
+    r = degrade_noise(F, r, (uint64_t)j);
+    g = degrade_noise(F, g, (uint64_t)(HW + j));
+    b = degrade_noise(F, b, (uint64_t)(2 * HW + j));
+  }
+  if (inside) r = g = b = F.j.m;
+}
+__device__ __forceinline__ bool in_rect(const JitterFrame& F, int64_t y, int64_t x) { return y >= F.y0 && y < F.y1 && x >= F.x0 && x < F.x1; }
+
+__device__ __forceinline__ f32x4 load4(const float* s) { return *reinterpret_cast<const f32x4*>(s); }
+__device__ __forceinline__ f32x4 load4(const uint8_t* s) {
+  const uint32_t w = *reinterpret_cast<const uint32_t*>(s);
+  f32x4 v;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = (float)((w >> (8 * e)) & 0xffu);
+  return v;
+}
+
+// pixels [lo, hi) of one unblurred frame: jitter_piece with the two pointwise stages
+template <typename T>
+__device__ __forceinline__ void degrade_piece(const DegradeFrame& F, const T* __restrict__ s, float* __restrict__ d, int64_t HW, uint32_t W,
+                                              int64_t lo, int64_t hi, bool first_piece, int head, bool vec_ok) {
+  const int tid = threadIdx.x;
+  const bool erase = F.j.erase != 0;
+  auto one = [&](int64_t j) {
+    float r = src_at(s, j), g = src_at(s, j + HW), b = src_at(s, j + 2 * HW);
+    int32_t y = 0;
+    uint32_t x = 0;
+    if (erase) jitter_pos(F.j, W, j, lo, y, x);
+    degrade_pixel(F, r, g, b, j, HW, erase && in_rect(F.j, y, x));
+    d[j] = r; d[j + HW] = g; d[j + 2 * HW] = b;
+  };
+  int64_t a = lo;
+  if (vec_ok) {
+    if (first_piece) {   // (lo == 0)
+      if (tid < head && tid < hi) one(tid);
+      a = head;
+    }
+    if (hi > a) {
+      const int64_t nv = (hi - a) / 4;
+      for (int64_t v = tid; v < nv; v += NT) {
+        const int64_t j = a + v * 4;
+        int32_t y = 0;
+        uint32_t x = 0;
+        if (erase) jitter_pos(F.j, W, j, lo, y, x);
+        f32x4 vr = load4(s + j), vg = load4(s + j + HW), vb = load4(s + j + 2 * HW);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float r = vr[e], g = vg[e], b = vb[e];
+          degrade_pixel(F, r, g, b, j + e, HW, erase && in_rect(F.j, y, x));
+          if (erase) jitter_next(W, y, x);
+          vr[e] = r; vg[e] = g; vb[e] = b;
+        }
+        *reinterpret_cast<f32x4*>(d + j) = vr;
+        *reinterpret_cast<f32x4*>(d + j + HW) = vg;
+        *reinterpret_cast<f32x4*>(d + j + 2 * HW) = vb;
+      }
+      a += nv * 4;
+    }
+  }
+  for (int64_t j = a + tid; j < hi; j += NT) one(j);
+}
+
+// index v of a row or column of n pixels, -n < v < 2 n - 1, mirrored at the border without repeating it
+__device__ __forceinline__ int64_t reflect(int64_t v, int64_t n) { return v < 0 ? -v : (v >= n ? 2 * (n - 1) - v : v); }
+
+// tile `tile` of one blurred frame: s, d = its first plane.  Every thread of the workgroup calls this.
+template <typename T>
+__device__ __forceinline__ void blur_tile(const DegradeFrame& F, const T* __restrict__ s, float* __restrict__ d, int H, int W, int R,
+                                          float sigma, int tile, float* lds) {
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int64_t HW = (int64_t)H * W;
+  const int tiles_x = (int)(((uint32_t)W + BLUR_TW - 1) / BLUR_TW);
+  const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+  const int64_t y0 = (int64_t)ty * BLUR_TH, x0 = (int64_t)tx * BLUR_TW;
+  const int th = (int)(H - y0 < BLUR_TH ? H - y0 : BLUR_TH), tw = (int)(W - x0 < BLUR_TW ? W - x0 : BLUR_TW);
+  const int ih = th + 2 * R, iw = tw + 2 * R;      // <= BLUR_IN_H, BLUR_IN_W: R <= BLUR_RMAX is checked on the host
+  float* in = lds;
+  float* mid = lds + 3 * BLUR_PLANE;
+  float* taps = mid + BLUR_MID;
+  if (tid <= R) taps[tid] = expf(-(float)(tid * tid) / (2.0f * sigma * sigma));
+  // the image's ih * iw pixels in row-major order, consecutive lanes on consecutive pixels; a lane issues the twelve loads of
+  // four pixels before it blends the first, so that two workgroups per compute unit are enough to cover the loads' latency
+  const int pixels = ih * iw;
+  for (int first = tid; first < pixels; first += NT * BLUR_LOADS) {
+    float r[BLUR_LOADS], g[BLUR_LOADS], b[BLUR_LOADS];
+    int o[BLUR_LOADS];
+#pragma unroll
+    for (int u = 0; u < BLUR_LOADS; ++u) {
+      const int idx = first + u * NT;
+      const bool inside = idx < pixels;                // (outside: pixel (0, 0) of the image is loaded and dropped)
+      const int ly = inside ? idx / iw : 0, lx = inside ? idx - ly * iw : 0;
+      const int64_t j = reflect(y0 - R + ly, H) * W + reflect(x0 - R + lx, W);
+      r[u] = src_at(s, j); g[u] = src_at(s, j + HW); b[u] = src_at(s, j + 2 * HW);
+      o[u] = inside ? ly * BLUR_IN_W + lx : -1;
+    }
+#pragma unroll
+    for (int u = 0; u < BLUR_LOADS; ++u) {
+      if (o[u] < 0) continue;
+      jitter_pixel<false>(F.j, r[u], g[u], b[u], 0, 0);
+      if (F.hue) hue_pixel(F.shift, r[u], g[u], b[u]);
+      in[o[u]] = r[u]; in[BLUR_PLANE + o[u]] = g[u]; in[2 * BLUR_PLANE + o[u]] = b[u];
+    }
+  }
+  __syncthreads();
+  float w[BLUR_RMAX + 1];
+  float side = 0.0f;
+#pragma unroll
+  for (int k = 1; k <= BLUR_RMAX; ++k) {
+    w[k] = k <= R ? taps[k] : 0.0f;
+    side += w[k];
+  }
+  w[0] = taps[0];
+  const float total = fmaf(2.0f, side, w[0]);
+#pragma unroll
+  for (int k = 0; k <= BLUR_RMAX; ++k) w[k] = w[k] / total;
+  const bool erase = F.j.erase != 0;
+#pragma unroll 1
+  for (int c = 0; c < 3; ++c) {
+    const float* pin = in + c * BLUR_PLANE;
+    if (lane < tw) {
+      for (int ly = wave; ly < ih; ly += NT / 64) {
+        const float* p = pin + ly * BLUR_IN_W + lane + R;
+        float acc = w[0] * p[0];
+#pragma unroll
+        for (int k = 1; k <= BLUR_RMAX; ++k)
+          if (k <= R) acc = fmaf(w[k], p[-k] + p[k], acc);
+        mid[ly * BLUR_TW + lane] = acc;
+      }
+    }
+    __syncthreads();
+    for (int q = tid; q < BLUR_TH * (BLUR_TW / 4); q += NT) {
+      const int oy = q / (BLUR_TW / 4), ox = (q % (BLUR_TW / 4)) * 4;
+      if (oy >= th || ox >= tw) continue;
+      const float* p = mid + (oy + R) * BLUR_TW + ox;
+      f32x4 acc = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[e] = w[0] * acc[e];
+#pragma unroll
+      for (int k = 1; k <= BLUR_RMAX; ++k) {
+        if (k <= R) {
+          const f32x4 up = *reinterpret_cast<const f32x4*>(p - k * BLUR_TW), down = *reinterpret_cast<const f32x4*>(p + k * BLUR_TW);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[e] = fmaf(w[k], up[e] + down[e], acc[e]);
+        }
+      }
+      const int64_t y = y0 + oy, x = x0 + ox;
+      const int64_t j = y * W + x;
+      const int valid = tw - ox < 4 ? tw - ox : 4;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (e < valid) {
+          if (F.noise) acc[e] = degrade_noise(F, acc[e], (uint64_t)(c * HW + j + e));
+          if (erase && in_rect(F.j, y, x + e)) acc[e] = F.j.m;
+        }
+      }
+      float* o = d + c * HW + j;
+      if (valid == 4 && ((uintptr_t)o & 15) == 0) {
+        *reinterpret_cast<f32x4*>(o) = acc;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (e < valid) o[e] = acc[e];
+      }
+    }
+    __syncthreads();                                // mid is rewritten by the next plane
+  }
+}
+
+__global__ __launch_bounds__(NT) void camera_degrade_kernel(const mmfn_camera_degrade_desc D, const int64_t* __restrict__ index, int64_t n,
+                                                            int pieces, int tiles) {
+  extern __shared__ __attribute__((aligned(16))) float degrade_lds[];
+  const int blk = (int)blockIdx.x, b = (int)blockIdx.y, s = (int)blockIdx.z, S = D.n_frames;
+  const int64_t HW = (int64_t)D.H * D.W, frame = 3 * HW;
+  const int esz = D.src_type == MMFN_GATHER_U8 ? 1 : 4;
+  const int align = D.src_type == MMFN_GATHER_U8 ? 4 : 16;   // bytes of a lane's load
+  int64_t i = index[b];
+  i = i < 0 ? 0 : (i >= n ? n - 1 : i);
+  const uint64_t id = (uint64_t)(D.sample_id ? D.sample_id[i] : i);
+  const uint64_t dkey = mmfn_rng_key(D.degrade_state, MMFN_RNG_STREAM_DEGRADE);
+  uint32_t q[5];
+#pragma unroll
+  for (int j = 0; j < 5; ++j) q[j] = mmfn_rng_u32(dkey, id * 8 + j) >> 8;
+  const bool blur = q[1] < D.blur_thresh;
+  if (blk >= (blur ? tiles : pieces)) return;                // (the same for every lane of the workgroup)
+  DegradeFrame F;                                            // (the same in every lane)
+  F.hue = D.hue != 0.0f;
+  F.shift = D.hue * draw_pm1(q[0]);
+  F.noise = q[3] < D.noise_thresh;
+  F.noise_std = fmaf(D.noise_std_hi - D.noise_std_lo, (float)q[4] * (1.0f / 16777216.0f), D.noise_std_lo);
+  F.noise_key = mmfn_rng_key(D.degrade_state, MMFN_RNG_STREAM_PIXEL_NOISE);
+  F.noise_base = (id * (uint64_t)S + (uint64_t)s) * (uint64_t)frame;
+  // the jitter's scalars, as camera_jitter_kernel works them out
+  const uint64_t key = mmfn_rng_key(D.state, MMFN_RNG_STREAM_JITTER);
+  uint32_t k[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) k[j] = mmfn_rng_u32(key, id * 8 + j) >> 8;
+  const float m = D.gray_mean[i * S + s];
+  JitterFrame& J = F.j;
+  J.m = m;
+  J.fb = fmaf(D.brightness, fmaf(2.0f, (float)k[0] * (1.0f / 16777216.0f), -1.0f), 1.0f);
+  J.fc = fmaf(D.contrast, fmaf(2.0f, (float)k[1] * (1.0f / 16777216.0f), -1.0f), 1.0f);
+  J.fs = fmaf(D.saturation, fmaf(2.0f, (float)k[2] * (1.0f / 16777216.0f), -1.0f), 1.0f);
+  J.tc = (1.0f - J.fc) * m;
+  J.erase = k[3] < D.erase_thresh;
+  J.y0 = J.y1 = J.x0 = J.x1 = J.row = 0;
+  J.col = 0;
+  const uintptr_t sa = (uintptr_t)D.src[s] + (uintptr_t)(i * frame) * esz;
+  const int head = (int)(((align - (sa & (align - 1))) & (align - 1)) / esz);
+  if (J.erase) {
+    const int32_t h = D.erase_h_min + (int32_t)(((uint64_t)k[4] * (uint64_t)(D.erase_h_max - D.erase_h_min + 1)) >> 24);
+    const int32_t w = D.erase_w_min + (int32_t)(((uint64_t)k[5] * (uint64_t)(D.erase_w_max - D.erase_w_min + 1)) >> 24);
+    J.y0 = (int32_t)(((uint64_t)k[7] * (uint64_t)(D.H - h + 1)) >> 24);
+    J.x0 = (int32_t)(((uint64_t)k[6] * (uint64_t)(D.W - w + 1)) >> 24);
+    J.y1 = J.y0 + h;
+    J.x1 = J.x0 + w;
+    if (blk && !blur) {   // the piece's first pixel
+      const int64_t lo0 = (int64_t)head + (int64_t)blk * JITTER_PIECE;
+      J.row = (int32_t)(lo0 / D.W);
+      J.col = (uint32_t)(lo0 % D.W);
+    }
+  }
+  const DegradeFrame& f = F;
+  float* d = D.dst + ((int64_t)b * S + s) * frame;
+  if (blur) {
+    const float sigma = fmaf(D.blur_sigma_hi - D.blur_sigma_lo, (float)q[2] * (1.0f / 16777216.0f), D.blur_sigma_lo);
+    if (D.src_type == MMFN_GATHER_U8)
+      blur_tile(f, reinterpret_cast<const uint8_t*>(D.src[s]) + i * frame, d, D.H, D.W, D.blur_radius, sigma, blk, degrade_lds);
+    else
+      blur_tile(f, reinterpret_cast<const float*>(D.src[s]) + i * frame, d, D.H, D.W, D.blur_radius, sigma, blk, degrade_lds);
+    return;
+  }
+  // vector accesses: as in camera_jitter_kernel
+  const bool vec_ok = HW % 4 == 0 && (((uintptr_t)(d + head)) & 15) == 0;
+  const int64_t lo = blk == 0 ? 0 : head + (int64_t)blk * JITTER_PIECE;
+  int64_t hi = head + (int64_t)(blk + 1) * JITTER_PIECE;
+  if (lo >= HW) return;
+  if (hi > HW) hi = HW;
+  if (D.src_type == MMFN_GATHER_U8)
+    degrade_piece(f, reinterpret_cast<const uint8_t*>(D.src[s]) + i * frame, d, HW, (uint32_t)D.W, lo, hi, blk == 0, head, vec_ok);
+  else
+    degrade_piece(f, reinterpret_cast<const float*>(D.src[s]) + i * frame, d, HW, (uint32_t)D.W, lo, hi, blk == 0, head, vec_ok);
+}
 }  // namespace
+
+extern "C" int mmfn_sizeof_camera_degrade_desc(void) { return (int)sizeof(mmfn_camera_degrade_desc); }
+extern "C" int mmfn_camera_degrade_tile_h(void) { return BLUR_TH; }
+extern "C" int mmfn_camera_degrade_tile_w(void) { return BLUR_TW; }
+
+extern "C" int mmfn_gather_camera_degrade(const mmfn_camera_degrade_desc* d, const int64_t* index, int B, int64_t n, void* stream) {
+  if (!d || !index || (uintptr_t)index % 8 || B < 0 || B > 65535) return MMFN_EINVAL;
+  if (d->n_frames < 1 || d->n_frames > MMFN_JITTER_MAX_FRAMES) return MMFN_EINVAL;
+  if (d->src_type != MMFN_GATHER_U8 && d->src_type != MMFN_GATHER_F32) return MMFN_EINVAL;
+  const int esz = d->src_type == MMFN_GATHER_F32 ? 4 : 1;
+  for (int s = 0; s < d->n_frames; ++s)
+    if (!d->src[s] || (uintptr_t)d->src[s] % esz) return MMFN_EINVAL;
+  if (!d->dst || (uintptr_t)d->dst % 4 || !d->gray_mean || (uintptr_t)d->gray_mean % 4 || !d->state || (uintptr_t)d->state % 8 ||
+      !d->degrade_state || (uintptr_t)d->degrade_state % 8 || (uintptr_t)d->sample_id % 8)
+    return MMFN_EINVAL;
+  if (d->H < 1 || d->W < 1) return MMFN_EINVAL;
+  const float strength[3] = {d->brightness, d->contrast, d->saturation};
+  for (float v : strength)
+    if (!(v >= 0.0f && v <= 1.0f)) return MMFN_EINVAL;   // (a NaN fails both comparisons)
+  if (d->erase_thresh > (1u << 24)) return MMFN_EINVAL;
+  if (d->erase_thresh > 0 && (d->erase_h_min < 1 || d->erase_h_min > d->erase_h_max || d->erase_h_max > d->H || d->erase_w_min < 1 ||
+                              d->erase_w_min > d->erase_w_max || d->erase_w_max > d->W))
+    return MMFN_EINVAL;
+  if (!(d->hue >= 0.0f && d->hue <= 0.5f)) return MMFN_EINVAL;
+  if (d->blur_thresh > (1u << 24) || d->noise_thresh > (1u << 24)) return MMFN_EINVAL;
+  if (d->blur_radius < 0 || d->blur_radius > MMFN_DEGRADE_MAX_RADIUS) return MMFN_EINVAL;
+  if (d->blur_thresh > 0) {
+    if (d->H <= d->blur_radius || d->W <= d->blur_radius) return MMFN_EINVAL;   // one mirror image must reach
+    if (!(d->blur_sigma_lo > 0.0f && d->blur_sigma_lo <= d->blur_sigma_hi && d->blur_sigma_hi <= 2.6666667f + 1e-6f)) return MMFN_EINVAL;
+  }
+  if (d->noise_thresh > 0 && !(d->noise_std_lo >= 0.0f && d->noise_std_lo <= d->noise_std_hi && d->noise_std_hi <= 64.0f)) return MMFN_EINVAL;
+  if (B == 0) return 0;
+  if (n < 1) return MMFN_EINVAL;
+  const int64_t pieces = ceil_div64((int64_t)d->H * d->W, JITTER_PIECE);   // (the first piece also takes the head, as in the gather)
+  const int64_t tiles = d->blur_thresh ? ceil_div64(d->H, BLUR_TH) * ceil_div64(d->W, BLUR_TW) : 0;
+  if (pieces > 0x7fffffff || tiles > 0x7fffffff) return MMFN_EINVAL;
+  hipLaunchKernelGGL(camera_degrade_kernel, dim3((unsigned)(pieces > tiles ? pieces : tiles), (unsigned)B, (unsigned)d->n_frames), dim3(NT),
+                     d->blur_thresh ? BLUR_LDS_BYTES : 0, (hipStream_t)stream, *d, index, n, (int)pieces, (int)tiles);
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
 
 extern "C" int mmfn_sizeof_gather_augment_desc(void) { return (int)sizeof(mmfn_gather_augment_desc); }
 

@@ -438,10 +438,16 @@ def palette_decode(codes, palette):
 # for this model - LiDAR histogram, lanes, target point and waypoints are untouched, no geometry to keep in sync.
 # The bird's-eye-view inputs are augmented the same way (Augment(lidar=LidarDropout(...), map=MapNoise(...)); one more launch,
 # mmfn_gather_augment): cells and one rectangle of the LiDAR histogram dropped, lanes dropped, the lane set moved rigidly and the
-# target point shifted, as localisation noise moves them in closed loop.  Not built: augmentation of PackedLoader / the pickle
+# target point shifted, as localisation noise moves them in closed loop.  The camera's sensor degradation - a hue shift, a
+# Gaussian blur and additive Gaussian noise (Augment(degrade=CameraDegrade(...))) - sits between the jitter's blends and its
+# rectangle in a launch that takes the jitter launch's place (mmfn_gather_camera_degrade): the blur is a neighbourhood operation,
+# so that kernel blends on load into LDS tiles and filters there.  Not built: augmentation of PackedLoader / the pickle
 # loaders, rotating or shifting the LiDAR image or the raster map (both need resampling and would disagree with the un-shifted
-# camera), radar, velocity or waypoint noise, hue, a random blend order.
+# camera), radar, velocity or waypoint noise, per-pixel dropout, a random stage order.
 RNG_STREAM_JITTER = 0x4A49      # csrc/common.h: MMFN_RNG_STREAM_JITTER
+RNG_STREAM_DEGRADE = 0x4447     # MMFN_RNG_STREAM_DEGRADE: a sample's degradation draws (hue, blur or not, sigma, noise or not, std)
+RNG_STREAM_PIXEL_NOISE = 0x504E  # MMFN_RNG_STREAM_PIXEL_NOISE: two draws per camera element
+DEGRADE_MAX_RADIUS = 8          # include/mmfn_hip.h: MMFN_DEGRADE_MAX_RADIUS
 RNG_STREAM_LIDAR = 0x4C44       # MMFN_RNG_STREAM_LIDAR: a sample's LiDAR draws (erase or not, the rectangle)
 RNG_STREAM_LIDAR_CELL = 0x4C43  # MMFN_RNG_STREAM_LIDAR_CELL: one draw per LiDAR element
 RNG_STREAM_MAP = 0x4D50         # MMFN_RNG_STREAM_MAP: a sample's map draws (shift, yaw, target shift)
@@ -556,16 +562,64 @@ class MapNoise(object):
         return bool(self.lanes_active or self.target_shift)
 
 
-class Augment(object):
-    """What ResidentLoader(augment=...) takes when more than the camera is augmented: camera = CameraJitter or None, lidar =
-    LidarDropout or None, map = MapNoise or None.  A part that is None, or whose strengths are all zero, leaves its fields in the
-    plain gather launch."""
+def _range(owner, nm, v, lo_open, top):
+    """(lo, hi) as floats with 0 <(=) lo <= hi <= top, ValueError otherwise (a NaN fails it too)."""
+    try:
+        lo, hi = (float(x) for x in v)
+    except (TypeError, ValueError):
+        raise ValueError("%s: %s is a (lo, hi) pair, got %r" % (owner, nm, v))
+    if not (lo <= hi <= top and (lo > 0.0 if lo_open else lo >= 0.0)):
+        raise ValueError("%s: %s needs 0 %s lo <= hi <= %g, got %r" % (owner, nm, "<" if lo_open else "<=", top, v))
+    return lo, hi
 
-    def __init__(self, camera=None, lidar=None, map=None):
-        for nm, v, cls in (("camera", camera, CameraJitter), ("lidar", lidar, LidarDropout), ("map", map, MapNoise)):
+
+class CameraDegrade(object):
+    """Settings of the resident loader's camera sensor degradation, applied between CameraJitter's blends and its erased
+    rectangle.  hue in [0, 0.5]: the sample's hue turns by hue * (2 u - 1) of a full circle (torchvision's ColorJitter(hue)
+    range); blur_prob: probability that a sample is blurred with a Gaussian whose sigma is uniform in blur_sigma = (lo, hi),
+    0 < lo <= hi <= 8/3 - the filter radius is fixed per object, radius = ceil(3 hi) <= 8, as torchvision's GaussianBlur fixes
+    its kernel size and varies sigma; noise_prob: probability that a sample gets additive Gaussian noise whose standard deviation
+    is uniform in noise_std = (lo, hi), 0 <= lo <= hi <= 64, in the image's 0..255 units.  seed as in CameraJitter: all frames of
+    a sample share its draws, the noise itself differs from frame to frame."""
+
+    def __init__(self, hue=0.0, blur_prob=0.0, blur_sigma=(0.5, 2.0), noise_prob=0.0, noise_std=(2.0, 12.0), seed=0):
+        self.hue = _prob("CameraDegrade", "hue", hue, 0.5)
+        self.blur_prob, self.noise_prob = _prob("CameraDegrade", "blur_prob", blur_prob), _prob("CameraDegrade", "noise_prob", noise_prob)
+        self.blur_sigma = _range("CameraDegrade", "blur_sigma", blur_sigma, True, 8.0 / 3.0)
+        self.noise_std = _range("CameraDegrade", "noise_std", noise_std, False, 64.0)
+        self.seed = int(seed)
+
+    @property
+    def radius(self):
+        """R: the filter takes the 2 R + 1 pixels around each one, whatever sigma a sample draws."""
+        return min(DEGRADE_MAX_RADIUS, int(np.ceil(3.0 * self.blur_sigma[1] - 1e-9)))
+
+    @property
+    def blur_thresh(self):
+        """The sample is blurred iff its 24-bit draw 1 is below this."""
+        return _thresh(self.blur_prob)
+
+    @property
+    def noise_thresh(self):
+        """The sample gets noise iff its 24-bit draw 3 is below this."""
+        return _thresh(self.noise_prob)
+
+    @property
+    def active(self):
+        return bool(self.hue or self.blur_thresh or self.noise_thresh)
+
+
+class Augment(object):
+    """What ResidentLoader(augment=...) takes when more than the camera's colours is augmented: camera = CameraJitter or None,
+    lidar = LidarDropout or None, map = MapNoise or None, degrade = CameraDegrade or None.  A part that is None, or whose
+    strengths are all zero, leaves its fields in the launch they would be in without it."""
+
+    def __init__(self, camera=None, lidar=None, map=None, degrade=None):
+        for nm, v, cls in (("camera", camera, CameraJitter), ("lidar", lidar, LidarDropout), ("map", map, MapNoise),
+                           ("degrade", degrade, CameraDegrade)):
             if v is not None and not isinstance(v, cls):
                 raise TypeError("Augment: %s takes a %s (or None), got %r" % (nm, cls.__name__, v))
-        self.camera, self.lidar, self.map = camera, lidar, map
+        self.camera, self.lidar, self.map, self.degrade = camera, lidar, map, degrade
 
 
 def _hash32(x):
@@ -632,19 +686,124 @@ def camera_jitter_reference(frames, gray_mean, draws, jitter):
     x = np.array(frames, dtype=np.float64)
     m = np.asarray(gray_mean, dtype=np.float64).reshape(-1)
     k = np.asarray(draws, dtype=np.int64).reshape(-1, 8)
-    N, _, H, W = x.shape
+    return _camera_erase(_camera_blends(x, m, k, jitter), m, k, jitter)
+
+
+def _camera_blends(x, m, k, jitter):
+    """The jitter's three blends on float64 frames [N, 3, H, W] (gray means m [N], draws k [N, 8])."""
     factor = lambda strength, j: (1.0 + float(np.float32(strength)) * (2.0 * (k[:, j] / 16777216.0) - 1.0))[:, None, None, None]
     f_b, f_c, f_s = factor(jitter.brightness, 0), factor(jitter.contrast, 1), factor(jitter.saturation, 2)
     x = np.clip(f_c * x + (1.0 - f_c) * m[:, None, None, None], 0.0, 255.0)
     x = np.clip(f_b * x, 0.0, 255.0)
     gray = 0.299 * x[:, 0:1] + 0.587 * x[:, 1:2] + 0.114 * x[:, 2:3]
-    x = np.clip(f_s * x + (1.0 - f_s) * gray, 0.0, 255.0)
-    for i in range(N):
+    return np.clip(f_s * x + (1.0 - f_s) * gray, 0.0, 255.0)
+
+
+def _camera_erase(x, m, k, jitter):
+    """The jitter's rectangle, in place: every channel of the erased pixels becomes the frame's gray mean."""
+    H, W = x.shape[2:]
+    for i in range(x.shape[0]):
         rect = erase_rectangle(k[i], jitter, H, W)
         if rect is not None:
             y0, x0, h, w = rect
             x[i, :, y0:y0 + h, x0:x0 + w] = m[i]
     return x
+
+
+def degrade_draws(seed, epoch, sample_ids):
+    """int64 [len(sample_ids), 8]: a sample's degradation draws (stream RNG_STREAM_DEGRADE): hue, blur or not, sigma, noise or
+    not, noise std; k_5..k_7 reserved."""
+    return _sample_draws(seed, epoch, RNG_STREAM_DEGRADE, sample_ids)
+
+
+def hue_shift_reference(x, shift):
+    """Stage 2 of mmfn_gather_camera_degrade in float64: x [..., 3, H, W] (any scale: the formulas divide only by the pixel's own
+    max and chroma), shift in turns, broadcast against x's leading axes + [1, 1].  torchvision's _rgb2hsv, h <- frac(h + shift),
+    _hsv2rgb."""
+    x = np.asarray(x, dtype=np.float64)
+    r, g, b = x[..., 0, :, :], x[..., 1, :, :], x[..., 2, :, :]
+    mx, mn = np.maximum(r, np.maximum(g, b)), np.minimum(r, np.minimum(g, b))
+    c = mx - mn
+    gray = mx == mn
+    s = c / np.where(gray, 1.0, mx)
+    inv = 1.0 / np.where(gray, 1.0, c)
+    rc, gc, bc = (mx - r) * inv, (mx - g) * inv, (mx - b) * inv
+    h6 = np.where(mx == r, bc - gc, np.where(mx == g, 2.0 + rc - bc, 4.0 + gc - rc))
+    h = h6 / 6.0 + shift
+    h = h - np.floor(h)
+    hs = h * 6.0
+    fl = np.floor(hs)
+    f = hs - fl
+    sector = fl.astype(np.int64) % 6
+    top = np.max(np.abs(x)) if x.size else 0.0
+    clamp = lambda v: np.clip(v, 0.0, max(top, 0.0))
+    p, q, t = clamp(mx * (1.0 - s)), clamp(mx * (1.0 - s * f)), clamp(mx * (1.0 - s * (1.0 - f)))
+    out = np.empty_like(x)
+    out[..., 0, :, :] = np.choose(sector, [mx, q, p, p, t, mx])
+    out[..., 1, :, :] = np.choose(sector, [t, mx, mx, q, p, p])
+    out[..., 2, :, :] = np.choose(sector, [p, p, t, mx, mx, q])
+    return out
+
+
+def gaussian_blur_reference(x, sigma, radius):
+    """Stage 3 in float64: x [..., H, W] filtered along W, then along H, with the 2 radius + 1 taps exp(-d^2 / (2 sigma^2)) over
+    their sum; outside the frame the pixel mirrored at the border without repeating it (numpy's and torch's "reflect")."""
+    x = np.asarray(x, dtype=np.float64)
+    R = int(radius)
+    d = np.arange(-R, R + 1, dtype=np.float64)
+    w = np.exp(-d * d / (2.0 * float(sigma) ** 2))
+    w /= w.sum()
+    lead = [(0, 0)] * (x.ndim - 2)
+    H, W = x.shape[-2:]
+    xp = np.pad(x, lead + [(0, 0), (R, R)], mode="reflect")
+    x = sum(w[k] * xp[..., :, k:k + W] for k in range(2 * R + 1))
+    xp = np.pad(x, lead + [(R, R), (0, 0)], mode="reflect")
+    return sum(w[k] * xp[..., k:k + H, :] for k in range(2 * R + 1))
+
+
+def pixel_noise_reference(seed, epoch, sample_id, n_frames, frame, shape):
+    """The standard normal draws of stage 4 for frame `frame` of sample `sample_id`, float64 [3, H, W]: element e draws at
+    2 q and 2 q + 1 of stream RNG_STREAM_PIXEL_NOISE, q = (id * n_frames + frame) * 3 H W + e in wrapping 64-bit arithmetic;
+    sqrt(-2 ln u1) cos(2 pi u2) with u1 = (k + 1) 2^-24, u2 = k' 2^-24."""
+    numel = int(np.prod(shape))
+    base = (((int(sample_id) & _M64) * int(n_frames) + int(frame)) * numel) & _M64
+    q = np.arange(numel, dtype=np.uint64) + np.asarray([base], dtype=np.uint64)          # (arrays wrap silently)
+    two = np.uint64(2)
+    k0 = (rng_u32(seed, epoch, RNG_STREAM_PIXEL_NOISE, q * two) >> np.uint64(8)).astype(np.float64)
+    k1 = (rng_u32(seed, epoch, RNG_STREAM_PIXEL_NOISE, q * two + np.uint64(1)) >> np.uint64(8)).astype(np.float64)
+    z = np.sqrt(-2.0 * np.log((k0 + 1.0) / 16777216.0)) * np.cos(2.0 * np.pi * (k1 / 16777216.0))
+    return z.reshape(shape)
+
+
+def camera_degrade_reference(frames, gray_mean, ids, epoch, jitter, degrade):
+    """What mmfn_gather_camera_degrade computes, in float64: frames [N, 3, H, W] (one frame per sample) or [N, S, 3, H, W] with
+    values 0..255, gray_mean [N] or [N, S] as in camera_jitter_reference, ids [N] the samples' global ids, jitter = CameraJitter
+    or None, degrade = CameraDegrade or None -> float64 of frames' shape.  The jitter's blends, hue, blur, noise, the jitter's
+    rectangle; a degrade that does nothing gives camera_jitter_reference's result."""
+    jitter = jitter if jitter is not None else CameraJitter()
+    degrade = degrade if degrade is not None else CameraDegrade()
+    x = np.array(frames, dtype=np.float64)
+    shape = x.shape
+    S = 1 if x.ndim == 4 else shape[1]
+    x = x.reshape((-1,) + shape[-3:])
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    m = np.asarray(gray_mean, dtype=np.float64).reshape(-1)
+    k = np.repeat(jitter_draws(jitter.seed, epoch, ids), S, axis=0)
+    q = np.repeat(degrade_draws(degrade.seed, epoch, ids), S, axis=0)
+    u = q / 16777216.0
+    f32 = lambda v: float(np.float32(v))
+    x = _camera_blends(x, m, k, jitter)
+    if degrade.hue != 0.0:
+        x = np.clip(hue_shift_reference(x, (f32(degrade.hue) * (2.0 * u[:, 0] - 1.0))[:, None, None]), 0.0, 255.0)
+    lo, hi = (f32(v) for v in degrade.blur_sigma)
+    n_lo, n_hi = (f32(v) for v in degrade.noise_std)
+    for f in range(x.shape[0]):
+        if q[f, 1] < degrade.blur_thresh:
+            x[f] = gaussian_blur_reference(x[f], lo + (hi - lo) * u[f, 2], degrade.radius)
+        if q[f, 3] < degrade.noise_thresh:
+            z = pixel_noise_reference(degrade.seed, epoch, ids[f // S], S, f % S, x[f].shape)
+            x[f] = np.clip(x[f] + (n_lo + (n_hi - n_lo) * u[f, 4]) * z, 0.0, 255.0)
+    return _camera_erase(x, m, k, jitter).reshape(shape)
 
 
 def lidar_dropout_reference(frames, ids, aug, epoch):
@@ -932,7 +1091,9 @@ class ResidentFrames(object):
         `augment` = {"sample_id": int64 [n], "camera": (CameraJitter, gray_mean, state), "lidar": (LidarDropout, state), "map":
         (MapNoise, state)}, each part optional: the LiDAR frames, the lane set and the target point a part touches leave the gather
         launch for one mmfn_gather_augment launch - at most three launches per batch.  ValueError for a lane-augmented batch of
-        more than 4096 lanes per sample."""
+        more than 4096 lanes per sample.  "degrade": (CameraDegrade, gray_mean, state) sends the camera field through
+        mmfn_gather_camera_degrade instead of the jitter launch, with the "camera" part's blends and rectangle if there is one:
+        still at most three launches."""
         from . import ops
         B, S, dev, T = len(rows), self.seq_len, self.device, self.tensors
         arrays = self.plan_["arrays"]
@@ -940,6 +1101,9 @@ class ResidentFrames(object):
         augment = augment or {}
         if jitter is None and "camera" in augment:
             jitter = tuple(augment["camera"]) + (augment["sample_id"],)
+        degrade = augment.get("degrade")
+        if degrade is not None and jitter is None:      # no blends, no rectangle: the launch still wants a state to read
+            jitter = (CameraJitter(), degrade[1], degrade[2], augment["sample_id"])
         lidar, noise = augment.get("lidar"), augment.get("map")
         move_lanes = noise is not None and noise[0].lanes_active
         move_target = noise is not None and noise[0].target_shift != 0.0
@@ -986,10 +1150,15 @@ class ResidentFrames(object):
             if jitter is not None:
                 aug, gray_mean, state, sample_id = jitter
                 H, W = self.shapes[arrays[0]][1:]
-                ops.gather_camera_jitter(self.camera_frames(), inp["image"], gray_mean, state, index, self.n,
-                                         brightness=aug.brightness, contrast=aug.contrast, saturation=aug.saturation,
-                                         erase_thresh=aug.erase_thresh, erase_h=aug.erase_bounds(H), erase_w=aug.erase_bounds(W),
-                                         sample_id=sample_id)
+                blends = dict(brightness=aug.brightness, contrast=aug.contrast, saturation=aug.saturation, erase_thresh=aug.erase_thresh,
+                              erase_h=aug.erase_bounds(H), erase_w=aug.erase_bounds(W), sample_id=sample_id)
+                if degrade is not None:
+                    deg = degrade[0]
+                    ops.gather_camera_degrade(self.camera_frames(), inp["image"], gray_mean, state, degrade[2], index, self.n,
+                                              hue=deg.hue, blur_thresh=deg.blur_thresh, blur_sigma=deg.blur_sigma, blur_radius=deg.radius,
+                                              noise_thresh=deg.noise_thresh, noise_std=deg.noise_std, **blends)
+                else:
+                    ops.gather_camera_jitter(self.camera_frames(), inp["image"], gray_mean, state, index, self.n, **blends)
             if lidar is not None or move_lanes or move_target:
                 parts = {}
                 if lidar is not None:
@@ -1028,7 +1197,9 @@ class ResidentLoader(object):
     and the sample ids, all on the device and none of them in the store.  `augment` = Augment(camera=, lidar=, map=) adds LiDAR
     dropout, lane dropout and map noise (LidarDropout, MapNoise): the fields they touch go through a third launch, each part with
     a state of its own; a part that is None or whose strengths are all zero stays in the plain launch, and Augment(camera=j) is
-    augment=j.  None (the default) is the plain path, bit for bit; build validation loaders without it.  PackedLoader and the
+    augment=j.  Augment(degrade=CameraDegrade(...)) adds a hue shift, a Gaussian blur and sensor noise to the camera frames: the
+    camera launch is then mmfn_gather_camera_degrade, with the camera part's blends and rectangle if there is one, and the loader
+    holds a degrade state (and the gray means and sample ids, with or without a CameraJitter).  None (the default) is the plain path, bit for bit; build validation loaders without it.  PackedLoader and the
     pickle loaders are not augmented."""
     device_resident = True
 
@@ -1054,7 +1225,15 @@ class ResidentLoader(object):
             if parts.map.lanes_active:
                 resident.lane_field()
             self.map_state = state()
-        if any(hasattr(self, nm) for nm in ("jitter_state", "lidar_state", "map_state")):
+        if parts.degrade is not None and parts.degrade.active:
+            if not hasattr(self, "gray_mean"):
+                self.gray_mean = self._gray_mean(resident)
+            H, W = resident.shapes[resident.plan_["arrays"][0]][1:]
+            if parts.degrade.blur_thresh and min(H, W) <= parts.degrade.radius:
+                raise ValueError("CameraDegrade: a blur of radius %d needs camera frames larger than that, these are %d x %d" % (
+                    parts.degrade.radius, H, W))
+            self.degrade_state = state()
+        if any(hasattr(self, nm) for nm in ("jitter_state", "lidar_state", "map_state", "degrade_state")):
             self.sample_id = torch.from_numpy(np.ascontiguousarray(resident.indices, dtype=np.int64)).to(resident.device)
 
     @staticmethod
@@ -1093,6 +1272,8 @@ class ResidentLoader(object):
             parts["lidar"] = (self.augment.lidar, put(self.lidar_state, self.augment.lidar.seed))
         if hasattr(self, "map_state"):
             parts["map"] = (self.augment.map, put(self.map_state, self.augment.map.seed))
+        if hasattr(self, "degrade_state"):
+            parts["degrade"] = (self.augment.degrade, self.gray_mean, put(self.degrade_state, self.augment.degrade.seed))
         if not parts:
             return {}
         parts["sample_id"] = self.sample_id

@@ -1418,6 +1418,36 @@ def gather_camera_jitter(srcs, dst, gray_mean, state, index, n, brightness=0.0, 
     return dst
 
 
+def gather_camera_degrade(srcs, dst, gray_mean, state, degrade_state, index, n, brightness=0.0, contrast=0.0, saturation=0.0,
+                          erase_thresh=0, erase_h=(1, 1), erase_w=(1, 1), hue=0.0, blur_thresh=0, blur_sigma=(0.5, 2.0), blur_radius=0,
+                          noise_thresh=0, noise_std=(0.0, 0.0), sample_id=None):
+    """gather_camera_jitter with a hue shift, a Gaussian blur and sensor noise between the blends and the erased rectangle, in one
+    launch (csrc/resident.hip, mmfn_gather_camera_degrade; formulas in include/mmfn_hip.h).  Arguments as there, plus
+    degrade_state: int64 [2] device = {seed, epoch} of the new draws; hue in [0, 0.5]; blur_thresh / noise_thresh = round(prob *
+    2^24); blur_sigma = (lo, hi) with 0 < lo <= hi <= 8/3; blur_radius = R in 0..8, below min(H, W); noise_std = (lo, hi) in the
+    image's 0..255 units.  Capturable: index, both states and sample_id are read by the kernel."""
+    if index.dtype != torch.int64 or not index.is_contiguous():
+        raise ValueError("gather_camera_degrade: index must be a contiguous int64 tensor")
+    if not 1 <= len(srcs) <= _lib.JITTER_MAX_FRAMES:
+        raise ValueError("gather_camera_degrade: 1..%d frames per sample, got %d" % (_lib.JITTER_MAX_FRAMES, len(srcs)))
+    if dst.dim() != 4 or dst.shape[1] != 3 or dst.dtype != torch.float32 or not dst.is_contiguous():
+        raise ValueError("gather_camera_degrade: dst must be a contiguous f32 [B * S, 3, H, W] tensor")
+    d = _lib.CameraDegradeDesc()
+    for s, t in enumerate(srcs):
+        if t is not None and (t.dtype != srcs[0].dtype or not t.is_contiguous() or (t.shape[0] and t[0].numel() != dst[0].numel())):
+            raise ValueError("gather_camera_degrade: every source is a contiguous [n, 3, H, W] tensor of one dtype")
+        d.src[s] = ptr(t)
+    d.dst, d.gray_mean, d.sample_id, d.state, d.degrade_state = ptr(dst), ptr(gray_mean), ptr(sample_id), ptr(state), ptr(degrade_state)
+    d.n_frames, d.H, d.W = len(srcs), dst.shape[2], dst.shape[3]
+    d.src_type = _lib.GATHER_U8 if srcs[0] is not None and srcs[0].dtype == torch.uint8 else _lib.GATHER_F32
+    d.brightness, d.contrast, d.saturation, d.erase_thresh = float(brightness), float(contrast), float(saturation), int(erase_thresh)
+    (d.erase_h_min, d.erase_h_max), (d.erase_w_min, d.erase_w_max) = (int(v) for v in erase_h), (int(v) for v in erase_w)
+    d.hue, d.blur_thresh, d.blur_radius, d.noise_thresh = float(hue), int(blur_thresh), int(blur_radius), int(noise_thresh)
+    (d.blur_sigma_lo, d.blur_sigma_hi), (d.noise_std_lo, d.noise_std_hi) = (float(v) for v in blur_sigma), (float(v) for v in noise_std)
+    _call("mmfn_gather_camera_degrade", ctypes.byref(d), ptr(index), index.numel(), int(n), stream())
+    return dst
+
+
 def gather_augment(index, n, sample_id=None, lidar=None, lanes=None, target=None, map_state=None):
     """The bird's-eye-view fields of one batch gathered AND augmented in one launch (csrc/resident.hip, mmfn_gather_augment); each
     of the three parts is a dict or None:
