@@ -831,6 +831,61 @@ int mmfn_sizeof_gather_augment_desc(void);
 /* d: HOST memory, copied into the launch (by value); n = samples in the store */
 int mmfn_gather_augment(const mmfn_gather_augment_desc* d, const int64_t* index, int B, int64_t n, void* stream);
 
+/* ---- radar dropout and noise, speed noise inside the gather (data.ResidentLoader(augment=data.Augment(radar=, speed=))) -------
+ * The radar returns [81, 5], their adjacency [81, 81] and the speed scalar of a batch, gathered by sample index and augmented in
+ * the same pass; `parts` says what the launch carries (MMFN_SIGNAL_RADAR | MMFN_SIGNAL_SPEED), the other part's members are not
+ * read.  A launch of its own beside mmfn_gather_batch, _camera_jitter / _camera_degrade and _augment, whose descriptors and
+ * kernels are untouched: a batch with these parts on costs one more small launch (about 28 KB per sample).
+ * Draws, integers only.  i = clamp(index[b], 0, n - 1); id = sample_id ? sample_id[i] : i; key_X = mmfn_rng_key(state, stream X)
+ *   with radar_state for MMFN_RNG_STREAM_RADAR (0x5244) and _RADAR_NOISE (0x524E) and speed_state for _SPEED (0x5350)
+ *   (csrc/common.h); state = {seed, epoch}.  Everything depends on (seed, epoch, id) alone.
+ *   The normal draw of an index q of a stream: n_0 = mmfn_rng_u32(key, 2 q) >> 8, n_1 = mmfn_rng_u32(key, 2 q + 1) >> 8,
+ *   u1 = (n_0 + 1) * 2^-24, u2 = n_1 * 2^-24, z = sqrtf(-2 logf(u1)) * cosf(6.2831855f * u2): the camera's sensor noise.
+ * Radar, rows [depth, altitude, azimuth, velocity, front/rear flag], f32:
+ *   A stored row whose five values all compare equal to zero is padding (what radar_to_size appends): it never draws and never
+ *   moves.  Any other stored row r (0..80) is kept iff (mmfn_rng_u32(key_RADAR, id * 128 + r) >> 8) >= point_thresh.  The kept rows
+ *   land in stored order at destination rows 0..kept-1, the rows from there to 80 are +0.0: a frame with fewer returns.
+ *   Column c = 0..3 of a kept row becomes fmaf(std_c, z, x) with std = (depth_std, angle_std, angle_std, velocity_std) and z the
+ *   normal draw q = (id * 128 + r) * 4 + c of key_RADAR_NOISE - r the STORED row, so a row's noise does not depend on the rows
+ *   dropped around it; column 0 is then fmaxf(., 0).  A column whose std is 0 is copied bit for bit (no clamp either), and so is
+ *   the flag, always.
+ *   adj[i][j] = out[j][1] - out[i][1], one f32 subtraction over all 81 x 81 entries of the rows WRITTEN, the zero rows included
+ *   (data.radar_adjacency; csrc/radar.hip reads its sign only).  The adjacency a store holds is the f32 rounding of a float64
+ *   difference, this one the f32 difference of rounded values: with nothing dropped or moved the two can differ in the last bit,
+ *   which is why a launch without this part must stay with the plain gather of the stored adjacency.
+ * Speed, [n] f32: 0.0 iff (mmfn_rng_u32(key_SPEED, id * 8 + 0) >> 8) < speed_drop_thresh; otherwise, with speed_std != 0,
+ *   fmaxf(fmaf(speed_std, z, v), fminf(v, 0)) with z from draws 1 and 2 of that stream (id * 8 + 1, id * 8 + 2): a speed that is
+ *   not negative stays so, a negative one is not clamped above itself; with speed_std == 0 the stored bits.
+ * index, sample_id and the states are DEVICE memory, read by the kernel: a captured launch follows them.  Any alignment of the
+ * destinations (their rows are 405 and 6561 floats, both odd): element stores, consecutive lanes on consecutive addresses.
+ * B == 0 returns 0 and launches nothing.
+ * MMFN_EINVAL, nothing launched: d or index NULL, index not 8-byte aligned; parts outside 1..3; a pointer of a carried part NULL
+ * or not aligned to its element (states, sample_id: 8 bytes; sample_id may be NULL); rows != 81; a threshold above 2^24;
+ * depth_std or velocity_std outside [0, 4], angle_std outside [0, 0.1], speed_std outside [0, 4], or NaN; B < 0, B > 65535, n < 1
+ * with B > 0. */
+#define MMFN_RADAR_ROWS 81
+#define MMFN_SIGNAL_RADAR 1
+#define MMFN_SIGNAL_SPEED 2
+typedef struct mmfn_radar_speed_desc {
+  const int64_t* sample_id;      /* DEVICE [n] global sample id of resident row i, or NULL = i */
+  const float* radar_src;        /* [n, 81, 5] */
+  float* radar_dst;              /* [B, 81, 5] */
+  float* adj_dst;                /* [B, 81, 81] */
+  const uint64_t* radar_state;   /* DEVICE [2] = {seed, epoch} */
+  const float* speed_src;        /* [n] */
+  float* speed_dst;              /* [B] */
+  const uint64_t* speed_state;   /* DEVICE [2] = {seed, epoch} */
+  int32_t parts;                 /* MMFN_SIGNAL_RADAR | MMFN_SIGNAL_SPEED */
+  int32_t rows;                  /* MMFN_RADAR_ROWS */
+  uint32_t point_thresh;         /* round(prob * 2^24), 0 = never */
+  float depth_std, angle_std, velocity_std;   /* metres in [0, 4], radians in [0, 0.1], m/s in [0, 4] */
+  uint32_t speed_drop_thresh;    /* round(prob * 2^24), 0 = never */
+  float speed_std;               /* m/s in [0, 4] */
+} mmfn_radar_speed_desc;
+int mmfn_sizeof_radar_speed_desc(void);
+/* d: HOST memory, copied into the launch (by value); n = samples in the store */
+int mmfn_gather_radar_speed(const mmfn_radar_speed_desc* d, const int64_t* index, int B, int64_t n, void* stream);
+
 /* ---- VectorNet polyline max-pool + concat (model_vec.py:269-282) -------------------------------- */
 /* Lane attention of VectorNet for QUERY 0 ONLY (model_vec.py:301-324 MaskSelfAttention, of which VectornetEncoder.forward
  * :412 consumes lane 0's row alone): any number of lanes, keys >= kv_len[b] masked as the reference's -1e9 fill, kv_len 0 =

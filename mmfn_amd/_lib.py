@@ -132,6 +132,20 @@ class GatherAugmentDesc(ctypes.Structure):
                 ("shift", _f32), ("yaw_rad", _f32), ("target_shift", _f32)]
 
 
+RADAR_ROWS = 81
+SIGNAL_RADAR, SIGNAL_SPEED = 1, 2
+
+
+class RadarSpeedDesc(ctypes.Structure):
+    """mmfn_radar_speed_desc (include/mmfn_hip.h): the radar returns, their adjacency and the speed of a batch, gathered and
+    augmented in one launch."""
+    _fields_ = [("sample_id", _vp), ("radar_src", _vp), ("radar_dst", _vp), ("adj_dst", _vp), ("radar_state", _vp),
+                ("speed_src", _vp), ("speed_dst", _vp), ("speed_state", _vp),
+                ("parts", _i32), ("rows", _i32), ("point_thresh", ctypes.c_uint32),
+                ("depth_std", _f32), ("angle_std", _f32), ("velocity_std", _f32),
+                ("speed_drop_thresh", ctypes.c_uint32), ("speed_std", _f32)]
+
+
 G16_NT, G16_CONV_FWD, G16_CONV_DGRAD, G16_TN, G16_CONV_WGRAD = 0, 1, 2, 3, 4
 EPI16_OUT_F32 = 1024
 EPI16_RES_F32 = 2048
@@ -203,6 +217,8 @@ def lib():
             raise MMFNLibraryError("mmfn_camera_degrade_desc layout mismatch between C and ctypes")
         if handle.mmfn_sizeof_gather_augment_desc() != ctypes.sizeof(GatherAugmentDesc):
             raise MMFNLibraryError("mmfn_gather_augment_desc layout mismatch between C and ctypes")
+        if handle.mmfn_sizeof_radar_speed_desc() != ctypes.sizeof(RadarSpeedDesc):
+            raise MMFNLibraryError("mmfn_radar_speed_desc layout mismatch between C and ctypes")
         _lib = handle
     return _lib
 

@@ -119,6 +119,11 @@ __device__ __forceinline__ uint64_t mmfn_rng_key(const uint64_t* state, uint32_t
 // mmfn_gather_camera_degrade, with a {seed, epoch} state of its own beside the jitter's
 #define MMFN_RNG_STREAM_DEGRADE 0x4447u
 #define MMFN_RNG_STREAM_PIXEL_NOISE 0x504Eu
+// streams of the resident loader's radar dropout (one draw per stored row), radar noise (two draws per row and column) and speed
+// noise (a sample's eight draws): mmfn_gather_radar_speed, the radar and the speed part each with a {seed, epoch} state of its own
+#define MMFN_RNG_STREAM_RADAR 0x5244u
+#define MMFN_RNG_STREAM_RADAR_NOISE 0x524Eu
+#define MMFN_RNG_STREAM_SPEED 0x5350u
 // keep-mask scale: 0 if dropped, 1/(1-p) if kept
 __device__ __forceinline__ float mmfn_dropout_scale(uint64_t key, uint64_t idx, float p, float inv_keep) {
   float u = (float)(mmfn_rng_u32(key, idx) >> 8) * (1.0f / 16777216.0f);

@@ -3,7 +3,8 @@
 // in three steps on two processors.  Values are only moved (and u8 widened, which is exact): no arithmetic - except in the second
 // entry point at the end of the file, which gathers the camera field alone and colour-jitters it on the way, and in the third, which
 // gathers the LiDAR frames, the lane set and the target point and drops cells and lanes and moves the map on the way, and in the
-// fourth, which is the second with a hue shift, a Gaussian blur (the one neighbourhood operation here: LDS tiles) and sensor noise.
+// fourth, which is the second with a hue shift, a Gaussian blur (the one neighbourhood operation here: LDS tiles) and sensor noise,
+// and in the fifth, which gathers the radar returns and the speed, drops and perturbs them and rebuilds the radar adjacency.
 //   dense field   dst[b] = f32(src[index[b]])
 //   coded field   dst[b] = palette[4-bit codes of src[index[b]]]: a few-valued float field kept at half a byte per element
 //   ragged field  rows [off[i], off[i+1]) of the concatenated source -> dst[b, :count]; rows count..Lmax-1 = +0.0; count -> int32
@@ -942,7 +943,113 @@ __global__ __launch_bounds__(NT) void camera_degrade_kernel(const mmfn_camera_de
   else
     degrade_piece(f, reinterpret_cast<const float*>(D.src[s]) + i * frame, d, HW, (uint32_t)D.W, lo, hi, blk == 0, head, vec_ok);
 }
+
+// ---- radar dropout and noise, speed noise inside the gather (mmfn_gather_radar_speed; draws and formulas: include/mmfn_hip.h) ----
+// One workgroup per batch sample: 405 radar floats in, 405 + 6561 out (28 KB), so the launch is B small workgroups and its time
+// is the launch's own.  Lanes 0..80 (the first two waves) each own a stored row: padding or not, kept or not, a ballot per wave
+// and the first wave's count through LDS place it (map_block's prefix scheme, one round).  Then every lane takes elements of the
+// kept rows - 324 values with their own logf / cosf where the column's std is not 0, 81 flags - to LDS and to the destination,
+// the zero rows follow, and after a barrier all lanes stream the adjacency out of the written column 1 in LDS: consecutive lanes
+// on consecutive addresses, element stores (both rows are odd counts of floats, so a sample's rows start at any 4-byte phase).
+// The LDS reads of the adjacency stride by 5 floats, which is odd: no bank conflicts.  The speed is the last lane's, in a wave
+// that has no row to decide.
+constexpr int RADAR_ROWS = MMFN_RADAR_ROWS, RADAR_ELEMS = RADAR_ROWS * 5, RADAR_ADJ = RADAR_ROWS * RADAR_ROWS;
+static_assert(RADAR_ROWS <= 128 && RADAR_ROWS <= NT, "a lane per stored row, draws at id * 128 + r");
+
+// the camera's sensor noise draw (degrade_noise) out of two 24-bit draws
+__device__ __forceinline__ float normal_draw(uint32_t n0, uint32_t n1) {
+  const float u1 = (float)(n0 + 1u) * (1.0f / 16777216.0f), u2 = (float)n1 * (1.0f / 16777216.0f);
+  return sqrtf(-2.0f * logf(u1)) * cosf(6.2831855f * u2);
+}
+
+__global__ __launch_bounds__(NT) void radar_speed_kernel(const mmfn_radar_speed_desc D, const int64_t* __restrict__ index, int64_t n) {
+  __shared__ float out[RADAR_ELEMS];               // the rows as written
+  __shared__ uint8_t kept_row[RADAR_ROWS];         // kept_row[p] = stored row that lands at destination row p
+  __shared__ int wave_count[NT / 64];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  int64_t i = index[b];
+  i = i < 0 ? 0 : (i >= n ? n - 1 : i);
+  const uint64_t id = (uint64_t)(D.sample_id ? D.sample_id[i] : i);
+  if ((D.parts & MMFN_SIGNAL_SPEED) && tid == NT - 1) {
+    const uint64_t key = mmfn_rng_key(D.speed_state, MMFN_RNG_STREAM_SPEED);
+    float v = D.speed_src[i];
+    if ((mmfn_rng_u32(key, id * 8) >> 8) < D.speed_drop_thresh) {
+      v = 0.0f;
+    } else if (D.speed_std != 0.0f) {
+      const float z = normal_draw(mmfn_rng_u32(key, id * 8 + 1) >> 8, mmfn_rng_u32(key, id * 8 + 2) >> 8);
+      v = fmaxf(fmaf(D.speed_std, z, v), fminf(v, 0.0f));
+    }
+    D.speed_dst[b] = v;
+  }
+  if (!(D.parts & MMFN_SIGNAL_RADAR)) return;        // (the same for every lane of the workgroup)
+  const float* src = D.radar_src + i * RADAR_ELEMS;
+  bool keep = false;
+  if (tid < RADAR_ROWS) {
+    const float* p = src + tid * 5;
+    const bool real = !(p[0] == 0.0f && p[1] == 0.0f && p[2] == 0.0f && p[3] == 0.0f && p[4] == 0.0f);
+    keep = real && !((mmfn_rng_u32(mmfn_rng_key(D.radar_state, MMFN_RNG_STREAM_RADAR), id * 128 + (uint64_t)tid) >> 8) < D.point_thresh);
+  }
+  const uint64_t wave_keep = __ballot(keep);
+  if ((tid & 63) == 0) wave_count[tid >> 6] = __popcll(wave_keep);
+  __syncthreads();
+  const int first = wave_count[0], kept = first + wave_count[1];     // (rows live in the first two waves only)
+  if (keep) kept_row[(tid >> 6 ? first : 0) + __popcll(wave_keep & ((1ull << (tid & 63)) - 1ull))] = (uint8_t)tid;
+  __syncthreads();
+  const uint64_t noise_key = mmfn_rng_key(D.radar_state, MMFN_RNG_STREAM_RADAR_NOISE);
+  float* d = D.radar_dst + (int64_t)b * RADAR_ELEMS;
+  const int n_kept = kept * 5;
+  for (int e = tid; e < n_kept; e += NT) {
+    const int p = e / 5, c = e - p * 5, r = kept_row[p];
+    float v = src[r * 5 + c];
+    const float std_c = c == 0 ? D.depth_std : (c == 3 ? D.velocity_std : (c == 4 ? 0.0f : D.angle_std));
+    if (std_c != 0.0f) {
+      const uint64_t q = (id * 128 + (uint64_t)r) * 4 + (uint64_t)c;
+      v = fmaf(std_c, normal_draw(mmfn_rng_u32(noise_key, 2 * q) >> 8, mmfn_rng_u32(noise_key, 2 * q + 1) >> 8), v);
+      if (c == 0) v = fmaxf(v, 0.0f);
+    }
+    out[e] = v;
+    d[e] = v;
+  }
+  for (int e = n_kept + tid; e < RADAR_ELEMS; e += NT) {
+    out[e] = 0.0f;
+    d[e] = 0.0f;
+  }
+  __syncthreads();
+  float* a = D.adj_dst + (int64_t)b * RADAR_ADJ;
+  for (int e = tid; e < RADAR_ADJ; e += NT) {
+    const int row = e / RADAR_ROWS, col = e - row * RADAR_ROWS;
+    a[e] = out[col * 5 + 1] - out[row * 5 + 1];
+  }
+}
 }  // namespace
+
+extern "C" int mmfn_sizeof_radar_speed_desc(void) { return (int)sizeof(mmfn_radar_speed_desc); }
+
+extern "C" int mmfn_gather_radar_speed(const mmfn_radar_speed_desc* d, const int64_t* index, int B, int64_t n, void* stream) {
+  if (!d || !index || (uintptr_t)index % 8 || B < 0 || B > 65535) return MMFN_EINVAL;
+  if (d->parts < 1 || d->parts > (MMFN_SIGNAL_RADAR | MMFN_SIGNAL_SPEED) || (uintptr_t)d->sample_id % 8) return MMFN_EINVAL;
+  if (d->parts & MMFN_SIGNAL_RADAR) {
+    if (!d->radar_src || (uintptr_t)d->radar_src % 4 || !d->radar_dst || (uintptr_t)d->radar_dst % 4 || !d->adj_dst ||
+        (uintptr_t)d->adj_dst % 4 || !d->radar_state || (uintptr_t)d->radar_state % 8)
+      return MMFN_EINVAL;
+    if (d->rows != MMFN_RADAR_ROWS || d->point_thresh > (1u << 24)) return MMFN_EINVAL;
+    if (!(d->depth_std >= 0.0f && d->depth_std <= 4.0f)) return MMFN_EINVAL;            // (a NaN fails both comparisons)
+    if (!(d->angle_std >= 0.0f && d->angle_std <= 0.1f)) return MMFN_EINVAL;
+    if (!(d->velocity_std >= 0.0f && d->velocity_std <= 4.0f)) return MMFN_EINVAL;
+  }
+  if (d->parts & MMFN_SIGNAL_SPEED) {
+    if (!d->speed_src || (uintptr_t)d->speed_src % 4 || !d->speed_dst || (uintptr_t)d->speed_dst % 4 || !d->speed_state ||
+        (uintptr_t)d->speed_state % 8)
+      return MMFN_EINVAL;
+    if (d->speed_drop_thresh > (1u << 24)) return MMFN_EINVAL;
+    if (!(d->speed_std >= 0.0f && d->speed_std <= 4.0f)) return MMFN_EINVAL;
+  }
+  if (B == 0) return 0;
+  if (n < 1) return MMFN_EINVAL;
+  hipLaunchKernelGGL(radar_speed_kernel, dim3((unsigned)B), dim3(NT), 0, (hipStream_t)stream, *d, index, n);
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
 
 extern "C" int mmfn_sizeof_camera_degrade_desc(void) { return (int)sizeof(mmfn_camera_degrade_desc); }
 extern "C" int mmfn_camera_degrade_tile_h(void) { return BLUR_TH; }

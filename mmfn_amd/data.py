@@ -441,9 +441,14 @@ def palette_decode(codes, palette):
 # target point shifted, as localisation noise moves them in closed loop.  The camera's sensor degradation - a hue shift, a
 # Gaussian blur and additive Gaussian noise (Augment(degrade=CameraDegrade(...))) - sits between the jitter's blends and its
 # rectangle in a launch that takes the jitter launch's place (mmfn_gather_camera_degrade): the blur is a neighbourhood operation,
-# so that kernel blends on load into LDS tiles and filters there.  Not built: augmentation of PackedLoader / the pickle
-# loaders, rotating or shifting the LiDAR image or the raster map (both need resampling and would disagree with the un-shifted
-# camera), radar, velocity or waypoint noise, per-pixel dropout, a random stage order.
+# so that kernel blends on load into LDS tiles and filters there.  The radar returns of a 'rad' store and the speed input of every
+# variant (Augment(radar=RadarNoise(...), speed=SpeedNoise(...))) go through a fourth, small launch (mmfn_gather_radar_speed):
+# returns dropped and closed up, depth, angles and velocity perturbed, the speed perturbed or zeroed - and the 81 x 81 adjacency,
+# a function of the radar rows, rebuilt from the rows that launch wrote, since the stored one no longer describes them.  The
+# rebuilt adjacency is the f32 difference of f32 values, the stored one the f32 rounding of a float64 difference: the two can
+# differ in the last bit, so an inactive radar part keeps the plain launch and the stored bits.  Not built: augmentation of
+# PackedLoader / the pickle loaders, rotating or shifting the LiDAR image or the raster map (both need resampling and would disagree
+# with the un-shifted camera), ghost radar returns, reordered radar rows, waypoint noise, per-pixel dropout, a random stage order.
 RNG_STREAM_JITTER = 0x4A49      # csrc/common.h: MMFN_RNG_STREAM_JITTER
 RNG_STREAM_DEGRADE = 0x4447     # MMFN_RNG_STREAM_DEGRADE: a sample's degradation draws (hue, blur or not, sigma, noise or not, std)
 RNG_STREAM_PIXEL_NOISE = 0x504E  # MMFN_RNG_STREAM_PIXEL_NOISE: two draws per camera element
@@ -453,6 +458,9 @@ RNG_STREAM_LIDAR_CELL = 0x4C43  # MMFN_RNG_STREAM_LIDAR_CELL: one draw per LiDAR
 RNG_STREAM_MAP = 0x4D50         # MMFN_RNG_STREAM_MAP: a sample's map draws (shift, yaw, target shift)
 RNG_STREAM_LANE = 0x4C4E        # MMFN_RNG_STREAM_LANE: one draw per lane
 AUGMENT_MAX_LANES = 4096        # include/mmfn_hip.h: MMFN_AUGMENT_MAX_LANES
+RNG_STREAM_RADAR = 0x5244       # MMFN_RNG_STREAM_RADAR: one draw per stored radar row (kept or not)
+RNG_STREAM_RADAR_NOISE = 0x524E  # MMFN_RNG_STREAM_RADAR_NOISE: two draws per radar row and column
+RNG_STREAM_SPEED = 0x5350       # MMFN_RNG_STREAM_SPEED: a sample's speed draws (dropped or not, the two of its normal draw)
 _M32, _M64 = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
 
 
@@ -609,17 +617,68 @@ class CameraDegrade(object):
         return bool(self.hue or self.blur_thresh or self.noise_thresh)
 
 
+class RadarNoise(object):
+    """Settings of the resident loader's radar augmentation ('rad' stores).  A radar sample is 81 rows [depth, altitude, azimuth,
+    velocity, front/rear flag], the returns a frame recorded and zero rows after them (radar_to_size).  point_drop: probability
+    that a return is left out, the others closing up in stored order with zero rows after them - a frame that recorded fewer;
+    depth_std (metres, [0, 4]), angle_std (radians, [0, 0.1], altitude and azimuth alike) and velocity_std (m/s, [0, 4]): standard
+    deviations of Gaussian noise on columns 0..3 of a kept return, the depth clamped at 0 from below.  Zero rows are never drawn for
+    and never move, the flag is never touched, and the adjacency of the batch is rebuilt from the rows written.  seed as in
+    CameraJitter."""
+
+    def __init__(self, point_drop=0.0, depth_std=0.0, angle_std=0.0, velocity_std=0.0, seed=0):
+        self.point_drop = _prob("RadarNoise", "point_drop", point_drop)
+        self.depth_std, self.angle_std = _prob("RadarNoise", "depth_std", depth_std, 4.0), _prob("RadarNoise", "angle_std", angle_std, 0.1)
+        self.velocity_std = _prob("RadarNoise", "velocity_std", velocity_std, 4.0)
+        self.seed = int(seed)
+
+    @property
+    def point_thresh(self):
+        """A return is dropped iff its 24-bit draw is below this."""
+        return _thresh(self.point_drop)
+
+    @property
+    def column_std(self):
+        """The standard deviations of columns 0..3 as the f32 values the kernel multiplies."""
+        return tuple(float(np.float32(v)) for v in (self.depth_std, self.angle_std, self.angle_std, self.velocity_std))
+
+    @property
+    def active(self):
+        return bool(self.point_thresh or self.depth_std or self.angle_std or self.velocity_std)
+
+
+class SpeedNoise(object):
+    """Settings of the resident loader's noise on the speed input (every variant).  std (m/s, [0, 4]): standard deviation of
+    Gaussian noise on `velocity`, the result kept from crossing zero (max(v + std z, min(v, 0))); drop_prob: probability that a
+    sample's speed is 0.0 instead - the usual remedy against a policy that copies its own speed into its waypoints.  seed as in
+    CameraJitter."""
+
+    def __init__(self, std=0.0, drop_prob=0.0, seed=0):
+        self.std, self.drop_prob = _prob("SpeedNoise", "std", std, 4.0), _prob("SpeedNoise", "drop_prob", drop_prob)
+        self.seed = int(seed)
+
+    @property
+    def drop_thresh(self):
+        """The speed is dropped iff the sample's 24-bit draw 0 is below this."""
+        return _thresh(self.drop_prob)
+
+    @property
+    def active(self):
+        return bool(self.std or self.drop_thresh)
+
+
 class Augment(object):
     """What ResidentLoader(augment=...) takes when more than the camera's colours is augmented: camera = CameraJitter or None,
-    lidar = LidarDropout or None, map = MapNoise or None, degrade = CameraDegrade or None.  A part that is None, or whose
-    strengths are all zero, leaves its fields in the launch they would be in without it."""
+    lidar = LidarDropout or None, map = MapNoise or None, degrade = CameraDegrade or None, radar = RadarNoise or None, speed =
+    SpeedNoise or None.  A part that is None, or whose strengths are all zero, leaves its fields in the launch they would be in
+    without it."""
 
-    def __init__(self, camera=None, lidar=None, map=None, degrade=None):
+    def __init__(self, camera=None, lidar=None, map=None, degrade=None, radar=None, speed=None):
         for nm, v, cls in (("camera", camera, CameraJitter), ("lidar", lidar, LidarDropout), ("map", map, MapNoise),
-                           ("degrade", degrade, CameraDegrade)):
+                           ("degrade", degrade, CameraDegrade), ("radar", radar, RadarNoise), ("speed", speed, SpeedNoise)):
             if v is not None and not isinstance(v, cls):
                 raise TypeError("Augment: %s takes a %s (or None), got %r" % (nm, cls.__name__, v))
-        self.camera, self.lidar, self.map, self.degrade = camera, lidar, map, degrade
+        self.camera, self.lidar, self.map, self.degrade, self.radar, self.speed = camera, lidar, map, degrade, radar, speed
 
 
 def _hash32(x):
@@ -870,6 +929,81 @@ def map_noise_reference(lanes, counts, target_point, ids, aug, epoch):
     return out, out_counts, tp
 
 
+def _normal(k0, k1):
+    """The camera's sensor noise draw out of two arrays of 24-bit draws, float64: sqrt(-2 ln u1) cos(2 pi u2), u1 = (k0 + 1) 2^-24,
+    u2 = k1 2^-24."""
+    k0, k1 = np.asarray(k0, dtype=np.float64), np.asarray(k1, dtype=np.float64)
+    return np.sqrt(-2.0 * np.log((k0 + 1.0) / 16777216.0)) * np.cos(2.0 * np.pi * (k1 / 16777216.0))
+
+
+def _radar_row_index(sample_ids):
+    """uint64 [N, 81]: id * 128 + r for stored row r of each sample (wraps mod 2^64)."""
+    ids = np.asarray(sample_ids, dtype=np.int64).reshape(-1)
+    return ids.astype(np.uint64)[:, None] * np.uint64(128) + np.arange(RADAR_ROWS, dtype=np.uint64)[None, :]
+
+
+def radar_draws(seed, epoch, sample_ids):
+    """int64 [len(sample_ids), 81]: the 24-bit draw of every stored radar row (stream RNG_STREAM_RADAR):
+    k_r = mmfn_rng_u32(key, id * 128 + r) >> 8; a row that is not padding is dropped iff k_r < point_thresh."""
+    return (rng_u32(seed, epoch, RNG_STREAM_RADAR, _radar_row_index(sample_ids)) >> np.uint64(8)).astype(np.int64)
+
+
+def radar_normals(seed, epoch, sample_ids):
+    """float64 [len(sample_ids), 81, 4]: the standard normal draw of column c of stored row r (stream RNG_STREAM_RADAR_NOISE):
+    draws 2 q and 2 q + 1 with q = (id * 128 + r) * 4 + c in wrapping 64-bit arithmetic - whatever happens to the other rows."""
+    q = _radar_row_index(sample_ids)[:, :, None] * np.uint64(4) + np.arange(4, dtype=np.uint64)[None, None, :]
+    two = np.uint64(2)
+    draw = lambda idx: rng_u32(seed, epoch, RNG_STREAM_RADAR_NOISE, idx) >> np.uint64(8)
+    return _normal(draw(q * two), draw(q * two + np.uint64(1)))
+
+
+def speed_draws(seed, epoch, sample_ids):
+    """int64 [len(sample_ids), 8]: a sample's speed draws (stream RNG_STREAM_SPEED): dropped or not, then the two draws of its
+    normal; k_3..k_7 unused."""
+    return _sample_draws(seed, epoch, RNG_STREAM_SPEED, sample_ids)
+
+
+def radar_keep_mask(radar, ids, aug, epoch):
+    """bool [N, 81]: True where stored row r of radar [N, 81, 5], the sample with global id ids[b], stays under aug = RadarNoise in
+    epoch `epoch`: it is not padding (its five values are not all zero) and its draw is not below point_thresh."""
+    real = (np.asarray(radar).reshape(-1, RADAR_ROWS, 5) != 0.0).any(axis=-1)
+    return real & (radar_draws(aug.seed, epoch, ids) >= aug.point_thresh)
+
+
+def radar_noise_reference(radar, ids, aug, epoch):
+    """What mmfn_gather_radar_speed writes for the stored radar rows radar [N, 81, 5] (f32 values) of the samples with global ids
+    `ids` [N] under aug = RadarNoise: (radar float64 [N, 81, 5], adjacency float64 [N, 81, 81]).  Kept rows close up in stored
+    order, the rows after them are +0.0; columns 0..3 of a kept row get std_c * z in float64 (std = depth, angle, angle, velocity),
+    the depth then clamped at 0 from below; a column whose std is 0 is copied, so its f32 bits survive, and so is the flag.
+    adjacency[b, i, j] = out[b, j, 1] - out[b, i, 1] over all rows (radar_adjacency of the rows written)."""
+    src = np.asarray(radar).reshape(-1, RADAR_ROWS, 5)
+    keep = radar_keep_mask(src, ids, aug, epoch)
+    x = src.astype(np.float64)
+    z = radar_normals(aug.seed, epoch, ids)
+    for c, std in enumerate(aug.column_std):
+        if std:
+            x[..., c] += std * z[..., c]
+            if c == 0:
+                x[..., 0] = np.maximum(x[..., 0], 0.0)
+    out = np.zeros(x.shape, dtype=np.float64)
+    for b in range(x.shape[0]):
+        rows = np.flatnonzero(keep[b])
+        out[b, :len(rows)] = x[b, rows]
+    return out, out[:, None, :, 1] - out[:, :, None, 1]
+
+
+def speed_noise_reference(velocity, ids, aug, epoch):
+    """What mmfn_gather_radar_speed writes for the stored speeds velocity [N] (f32 values) under aug = SpeedNoise: float64 [N].
+    +0.0 where the sample's draw 0 is below drop_thresh; otherwise max(v + std z, min(v, 0)) with z from draws 1 and 2, or the
+    stored value itself with std = 0."""
+    v = np.array(velocity, dtype=np.float64).reshape(-1)
+    k = speed_draws(aug.seed, epoch, ids)
+    std = float(np.float32(aug.std))
+    out = np.maximum(v + std * _normal(k[:, 1], k[:, 2]), np.minimum(v, 0.0)) if std else v.copy()
+    out[k[:, 0] < aug.drop_thresh] = 0.0
+    return out
+
+
 class ResidentFrames(object):
     """A PackedFrames store (or the static shard `indices` of it) in device memory, reduced to what the `variant`'s engine input
     reads: camera and LiDAR frames, target point, velocity, waypoints; lane sets (vec, rad) or raster maps (img); radar and
@@ -1083,6 +1217,19 @@ class ResidentFrames(object):
             raise ValueError("map noise needs f32 lanes of [nodes, 5]; field %s is %s %s" % (nm, str(t.dtype).replace("torch.", ""), list(shape)))
         return t, self.tensors[nm + ".row_off"]
 
+    def radar_field(self):
+        """The resident radar rows f32 [n, 405] after checking that the radar launch can take them: ValueError for a store without
+        a radar field (variants 'vec' and 'img') or one that is not f32 [81, 5] with an [81, 81] adjacency."""
+        if self.variant != "rad":
+            raise ValueError("RadarNoise acts on the radar returns, which a %r store does not hold (SpeedNoise works on every "
+                             "variant)" % (self.variant,))
+        nm, adj = self.plan_["arrays"][2 * self.seq_len + 1:2 * self.seq_len + 3]
+        shape, t = self.shapes[nm], self.tensors[nm]
+        if shape != (RADAR_ROWS, 5) or self.shapes[adj] != (RADAR_ROWS, RADAR_ROWS) or t.dtype != torch.float32 or nm + ".palette" in self.tensors:
+            raise ValueError("radar noise needs f32 radar rows of [%d, 5] with a [%d, %d] adjacency; field %s is %s %s, %s is %s" % (
+                RADAR_ROWS, RADAR_ROWS, RADAR_ROWS, nm, str(t.dtype).replace("torch.", ""), list(shape), adj, list(self.shapes[adj])))
+        return t
+
     def gather(self, index, rows, lane_bucket=None, jitter=None, augment=None):
         """(engine input dict, gt) of the batch whose resident rows are `rows` (host) = `index` (int64 device tensor, the same
         values): fresh tensors from the caching allocator and one gather launch on the current stream.  `jitter` = (CameraJitter,
@@ -1093,7 +1240,8 @@ class ResidentFrames(object):
         launch for one mmfn_gather_augment launch - at most three launches per batch.  ValueError for a lane-augmented batch of
         more than 4096 lanes per sample.  "degrade": (CameraDegrade, gray_mean, state) sends the camera field through
         mmfn_gather_camera_degrade instead of the jitter launch, with the "camera" part's blends and rectangle if there is one:
-        still at most three launches."""
+        still at most three launches.  "radar": (RadarNoise, state) takes radar and radar_adj, "speed": (SpeedNoise, state) takes
+        velocity out of the gather launch and into one mmfn_gather_radar_speed launch, the fourth."""
         from . import ops
         B, S, dev, T = len(rows), self.seq_len, self.device, self.tensors
         arrays = self.plan_["arrays"]
@@ -1107,6 +1255,7 @@ class ResidentFrames(object):
         lidar, noise = augment.get("lidar"), augment.get("map")
         move_lanes = noise is not None and noise[0].lanes_active
         move_target = noise is not None and noise[0].target_shift != 0.0
+        radar, speed = augment.get("radar"), augment.get("speed")
 
         def frames(names, plain=True):   # frame s of sample b -> batch entry b * S + s, as MMFN._pack interleaves them
             shape = self.shapes[names[0]]
@@ -1126,7 +1275,7 @@ class ResidentFrames(object):
             return out
 
         inp = {"image": frames(arrays[:S], plain=jitter is None), "lidar": frames(arrays[S:2 * S], plain=lidar is None),
-               "target_point": dense("target_point", (2,), plain=not move_target), "velocity": dense("velocity", ())}
+               "target_point": dense("target_point", (2,), plain=not move_target), "velocity": dense("velocity", (), plain=speed is None)}
         if self.variant == "img":
             inp["map"] = frames(arrays[2 * S:3 * S])
         else:
@@ -1142,8 +1291,8 @@ class ResidentFrames(object):
                 fields.append(ops.gather_field(T[nm], inp["lane"], row_elems=T[nm].shape[1], row_off=T[nm + ".row_off"],
                                                count_out=inp["lane_num"], lmax=lmax))
         if self.variant == "rad":
-            inp["radar"] = dense(arrays[2 * S + 1], (RADAR_ROWS, 5))
-            inp["radar_adj"] = dense(arrays[2 * S + 2], (RADAR_ROWS, RADAR_ROWS))
+            inp["radar"] = dense(arrays[2 * S + 1], (RADAR_ROWS, 5), plain=radar is None)
+            inp["radar_adj"] = dense(arrays[2 * S + 2], (RADAR_ROWS, RADAR_ROWS), plain=radar is None)
         gt = dense("waypoints", tuple(T["waypoints"].shape[1:]))
         if B:
             ops.gather_batch(fields, index, self.n)
@@ -1174,6 +1323,17 @@ class ResidentFrames(object):
                 if move_target:
                     parts["target"] = dict(src=T["target_point"], dst=inp["target_point"], shift=noise[0].target_shift)
                 ops.gather_augment(index, self.n, sample_id=augment["sample_id"], map_state=noise[1] if noise is not None else None, **parts)
+            if radar is not None or speed is not None:
+                parts = {}
+                if radar is not None:
+                    aug, state = radar
+                    depth_std, angle_std, _, velocity_std = aug.column_std
+                    parts["radar"] = dict(src=self.radar_field(), dst=inp["radar"], adj=inp["radar_adj"], state=state,
+                                          point_thresh=aug.point_thresh, depth_std=depth_std, angle_std=angle_std, velocity_std=velocity_std)
+                if speed is not None:
+                    aug, state = speed
+                    parts["speed"] = dict(src=T["velocity"], dst=inp["velocity"], state=state, drop_thresh=aug.drop_thresh, std=aug.std)
+                ops.gather_radar_speed(index, self.n, sample_id=augment["sample_id"], **parts)
         return inp, gt
 
 
@@ -1199,7 +1359,10 @@ class ResidentLoader(object):
     a state of its own; a part that is None or whose strengths are all zero stays in the plain launch, and Augment(camera=j) is
     augment=j.  Augment(degrade=CameraDegrade(...)) adds a hue shift, a Gaussian blur and sensor noise to the camera frames: the
     camera launch is then mmfn_gather_camera_degrade, with the camera part's blends and rectangle if there is one, and the loader
-    holds a degrade state (and the gray means and sample ids, with or without a CameraJitter).  None (the default) is the plain path, bit for bit; build validation loaders without it.  PackedLoader and the
+    holds a degrade state (and the gray means and sample ids, with or without a CameraJitter).  Augment(radar=RadarNoise(...),
+    speed=SpeedNoise(...)) drops and perturbs the radar returns of a 'rad' store (ValueError on another variant) and rebuilds their
+    adjacency, and perturbs or zeroes the speed input of any variant: radar, radar_adj and velocity then go through a fourth, small
+    launch (mmfn_gather_radar_speed), each part with a state of its own (radar_state, speed_state).  None (the default) is the plain path, bit for bit; build validation loaders without it.  PackedLoader and the
     pickle loaders are not augmented."""
     device_resident = True
 
@@ -1233,7 +1396,12 @@ class ResidentLoader(object):
                 raise ValueError("CameraDegrade: a blur of radius %d needs camera frames larger than that, these are %d x %d" % (
                     parts.degrade.radius, H, W))
             self.degrade_state = state()
-        if any(hasattr(self, nm) for nm in ("jitter_state", "lidar_state", "map_state", "degrade_state")):
+        if parts.radar is not None and parts.radar.active:
+            resident.radar_field()
+            self.radar_state = state()
+        if parts.speed is not None and parts.speed.active:
+            self.speed_state = state()
+        if any(hasattr(self, nm) for nm in ("jitter_state", "lidar_state", "map_state", "degrade_state", "radar_state", "speed_state")):
             self.sample_id = torch.from_numpy(np.ascontiguousarray(resident.indices, dtype=np.int64)).to(resident.device)
 
     @staticmethod
@@ -1274,6 +1442,10 @@ class ResidentLoader(object):
             parts["map"] = (self.augment.map, put(self.map_state, self.augment.map.seed))
         if hasattr(self, "degrade_state"):
             parts["degrade"] = (self.augment.degrade, self.gray_mean, put(self.degrade_state, self.augment.degrade.seed))
+        if hasattr(self, "radar_state"):
+            parts["radar"] = (self.augment.radar, put(self.radar_state, self.augment.radar.seed))
+        if hasattr(self, "speed_state"):
+            parts["speed"] = (self.augment.speed, put(self.speed_state, self.augment.speed.seed))
         if not parts:
             return {}
         parts["sample_id"] = self.sample_id

@@ -1505,6 +1505,46 @@ def gather_augment(index, n, sample_id=None, lidar=None, lanes=None, target=None
     _call("mmfn_gather_augment", ctypes.byref(d), ptr(index), index.numel(), int(n), stream())
 
 
+def gather_radar_speed(index, n, sample_id=None, radar=None, speed=None):
+    """The radar returns and the speed of one batch gathered AND augmented in one launch (csrc/resident.hip,
+    mmfn_gather_radar_speed; draws and formulas in include/mmfn_hip.h); each of the two parts is a dict or None:
+      radar = dict(src = f32 [n, 81, 5] (or [n, 405]), dst = f32 [B, 81, 5], adj = f32 [B, 81, 81], state = int64 [2] {seed, epoch},
+              point_thresh, depth_std, angle_std, velocity_std): rows dropped and closed up, columns 0..3 perturbed, and the
+              adjacency adj[i][j] = dst[j][1] - dst[i][1] rebuilt from the rows written
+      speed = dict(src = f32 [n], dst = f32 [B], state = int64 [2] {seed, epoch}, drop_thresh, std)
+    index: int64 device [B]; sample_id: int64 device [n] or None (= the row).  Thresholds are round(prob * 2^24).  Capturable: index,
+    sample_id and the states are read by the kernel."""
+    if index.dtype != torch.int64 or not index.is_contiguous():
+        raise ValueError("gather_radar_speed: index must be a contiguous int64 tensor")
+    d = _lib.RadarSpeedDesc()
+    d.sample_id = ptr(sample_id)
+    B = index.numel()
+    if radar is not None:
+        src, dst, adj = radar["src"], radar["dst"], radar["adj"]
+        R = _lib.RADAR_ROWS
+        if tuple(dst.shape) != (B, R, 5) or dst.dtype != torch.float32 or not dst.is_contiguous():
+            raise ValueError("gather_radar_speed: the radar dst must be a contiguous f32 [B, %d, 5] tensor" % R)
+        if tuple(adj.shape) != (B, R, R) or adj.dtype != torch.float32 or not adj.is_contiguous():
+            raise ValueError("gather_radar_speed: the adjacency dst must be a contiguous f32 [B, %d, %d] tensor" % (R, R))
+        if src is not None and (src.dtype != torch.float32 or not src.is_contiguous() or src.shape[0] < n
+                                or int(torch.Size(src.shape[1:]).numel()) != R * 5):
+            raise ValueError("gather_radar_speed: the radar source is a contiguous f32 [n, %d, 5] tensor" % R)
+        d.parts |= _lib.SIGNAL_RADAR
+        d.radar_src, d.radar_dst, d.adj_dst, d.radar_state, d.rows = ptr(src), ptr(dst), ptr(adj), ptr(radar["state"]), R
+        d.point_thresh = int(radar.get("point_thresh", 0))
+        d.depth_std, d.angle_std, d.velocity_std = (float(radar.get(k, 0.0)) for k in ("depth_std", "angle_std", "velocity_std"))
+    if speed is not None:
+        src, dst = speed["src"], speed["dst"]
+        if dst.numel() != B or dst.dtype != torch.float32 or not dst.is_contiguous():
+            raise ValueError("gather_radar_speed: the speed dst must be a contiguous f32 [B] tensor")
+        if src is not None and (src.dtype != torch.float32 or not src.is_contiguous() or src.numel() < n):
+            raise ValueError("gather_radar_speed: the speed source is a contiguous f32 [n] tensor")
+        d.parts |= _lib.SIGNAL_SPEED
+        d.speed_src, d.speed_dst, d.speed_state = ptr(src), ptr(dst), ptr(speed["state"])
+        d.speed_drop_thresh, d.speed_std = int(speed.get("drop_thresh", 0)), float(speed.get("std", 0.0))
+    _call("mmfn_gather_radar_speed", ctypes.byref(d), ptr(index), B, int(n), stream())
+
+
 def polyline_pool_fwd(y, out, arg, R, V, H, last):
     _call("mmfn_polyline_pool_fwd_f32", ptr(y), ptr(out), ptr(arg), R, V, H, 1 if last else 0, stream())
     return out
