@@ -563,6 +563,28 @@ int mmfn_adamw_rows_f32(float* p, const float* g, float* m, float* v, int64_t n,
                         int n_groups, const int32_t* rows, int n_rows, const int64_t* class_steps, int n_classes, int variant,
                         const float* coef, float* avg, const int64_t* n_averaged, const float* ema_w, int avg_mode, const int32_t* ok,
                         void* stream);
+
+/* The amsgrad variant (torch.optim.AdamW(amsgrad=True), the single-tensor non-capturable form) of the two launches above, in the
+ * same single pass.  vmax (n floats, 16-byte aligned, never NULL) is torch's max_exp_avg_sq: per element, after m and v are
+ * updated as above,
+ *     vmax = maximum(vmax, v_new)   (torch.maximum: NaN when either operand is NaN)
+ *     p    = p * decay - step_size * (m_new / (sqrtf(vmax) / bc2_sqrt + eps))
+ * amsgrad is a per-group property: the LAST float of a hyper row ({lr, beta1, beta2, eps, weight_decay, grad_scale, -, amsgrad})
+ * switches it on when it is not 0.  A float4 of a group whose flag is 0 neither loads nor stores vmax and gets the bits of
+ * mmfn_adamw_groups_f32 / mmfn_adamw_rows_f32; with every flag 0 the launch equals that entry point bit for bit.  A frozen float4
+ * touches none of p / m / v / vmax (p alone with AVG); a GUARD instance with *ok == 0 touches nothing.  variant, and every other
+ * argument, as in the entry point without _ams; any NULL or misaligned pointer the launch would read: MMFN_EINVAL.
+ * 36 B per parameter of an amsgrad group instead of 28. */
+int mmfn_adamw_groups_ams_f32(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, const uint8_t* group_of,
+                              const float* hyper, int n_groups, const int64_t* step, int variant, const float* coef, float* avg,
+                              const int64_t* n_averaged, const float* ema_w, int avg_mode, const int32_t* ok, void* stream);
+int mmfn_adamw_rows_ams_f32(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, const uint8_t* row_of,
+                            const float* hyper, int n_groups, const int32_t* rows, int n_rows, const int64_t* class_steps,
+                            int n_classes, int variant, const float* coef, float* avg, const int64_t* n_averaged, const float* ema_w,
+                            int avg_mode, const int32_t* ok, void* stream);
+/* the cap of the grid of the grouped / rows AdamW launches (256 threads, one float4 each): a range of more than 1024 * this many
+ * floats goes round their grid-stride loops again */
+int mmfn_adamw_max_blocks(void);
 /* class_steps[c] += 1 for every c < n_classes with active[c] != 0 (device bytes); ok (may be NULL): only when *ok (the guard) */
 int mmfn_class_steps_advance(int64_t* class_steps, const uint8_t* active, int n_classes, const int32_t* ok, void* stream);
 

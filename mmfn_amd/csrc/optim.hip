@@ -196,7 +196,8 @@ __global__ __launch_bounds__(256) void weight_average_kernel(const float* __rest
   }
 }
 
-int adamw_blocks(int64_t n) { return (int)std::min<int64_t>(ceil_div64(n / 4, 256), 4096); }
+constexpr int kAdamwMaxBlocks = 4096;   // beyond 4 * 256 * this many floats the grid-stride loops go round again
+int adamw_blocks(int64_t n) { return (int)std::min<int64_t>(ceil_div64(n / 4, 256), kAdamwMaxBlocks); }
 
 bool adamw_args_ok(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, int n_groups, const int64_t* step) {
   return step && hyper && n_groups >= 1 && n_groups <= MMFN_ADAMW_MAX_GROUPS && !(n & 3) &&
@@ -355,6 +356,182 @@ extern "C" int mmfn_adamw_rows_f32(float* p, const float* g, float* m, float* v,
   MMFN_LAUNCH_CHECK();
   return 0;
 }
+
+// ---- amsgrad (torch.optim.AdamW(amsgrad=True), the single-tensor non-capturable form) ------------------------------------------
+// A fifth stream vmax holds the running maximum of the second moment: vmax = maximum(vmax, v_new), and the denominator is built
+// from sqrtf(vmax) instead of sqrtf(v_new).  amsgrad is a per-group property: hyper[group][7] != 0 switches it on, and a float4 of
+// a group without it neither loads nor stores vmax and gets the bits of adamw_groups_kernel.  Kernels of their own and not a
+// branch of the ones above, which keep their code.  36 B per parameter of an amsgrad group instead of 28.
+namespace {
+// one group's (one row's) scalars with the expressions of adamw_groups_kernel; pad carries the amsgrad flag
+template <bool COEF>
+__device__ inline GroupScalars ams_scalars(const float* __restrict__ h, double t, const float* __restrict__ coef) {
+  const double lr = (double)h[0], beta1 = (double)h[1], beta2 = (double)h[2];
+  GroupScalars s;
+  s.step_size = (float)(lr / (1.0 - pow(beta1, t)));
+  s.decay = (float)(1.0 - lr * (double)h[4]);
+  s.bc2_sqrt = (float)sqrt(1.0 - pow(beta2, t));
+  s.beta1 = h[1]; s.beta2 = h[2]; s.eps = h[3]; s.grad_scale = COEF ? h[5] * *coef : h[5]; s.pad = h[7];
+  return s;
+}
+
+// torch.maximum: NaN when either operand is NaN (fmaxf would drop it)
+__device__ inline float max_nan(float a, float b) { return (a == a && !(b <= a)) ? b : a; }
+
+// One float4 of the step; returns the new parameter.  The element arithmetic is written out operation by operation, with the
+// contractions the compiler chose for adamw_groups_kernel as explicit fmaf calls and contraction switched off for the rest, so
+// that the bits do not depend on what else reads the values here: g * grad_scale - m is one fma, so are the two moment updates
+// and p * decay - step_size * q.
+__device__ inline f32x4 adamw_ams_float4(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                         float* __restrict__ v, float* __restrict__ vmax, int64_t i, const GroupScalars& s) {
+#pragma clang fp contract(off)
+  const bool ams = s.pad != 0.f;
+  f32x4 pv = *reinterpret_cast<f32x4*>(p + i * 4);
+  const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i * 4);
+  f32x4 mv = *reinterpret_cast<f32x4*>(m + i * 4);
+  f32x4 vv = *reinterpret_cast<f32x4*>(v + i * 4);
+  f32x4 xv = vv;
+  if (ams) xv = *reinterpret_cast<f32x4*>(vmax + i * 4);
+  const float omb1 = 1.0f - s.beta1, omb2 = 1.0f - s.beta2;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float gg = gv[e] * s.grad_scale;
+    mv[e] = __builtin_fmaf(omb1, __builtin_fmaf(gv[e], s.grad_scale, -mv[e]), mv[e]);
+    vv[e] = __builtin_fmaf(s.beta2, vv[e], gg * (omb2 * gg));
+    xv[e] = ams ? max_nan(xv[e], vv[e]) : vv[e];
+    const float denom = sqrtf(xv[e]) / s.bc2_sqrt + s.eps;
+    pv[e] = __builtin_fmaf(s.decay, pv[e], -(s.step_size * (mv[e] / denom)));
+  }
+  *reinterpret_cast<f32x4*>(p + i * 4) = pv;
+  *reinterpret_cast<f32x4*>(m + i * 4) = mv;
+  *reinterpret_cast<f32x4*>(v + i * 4) = vv;
+  if (ams) *reinterpret_cast<f32x4*>(vmax + i * 4) = xv;
+  return pv;
+}
+
+// the average's update of one float4 from the parameter pf, as the AVG branches of adamw_groups_kernel do it
+__device__ inline void avg_float4(const AvgArgs& avg, int64_t i, f32x4 pf) {
+  f32x4 out = pf;
+  if (*avg.n_averaged != 0) out = lerp4(*reinterpret_cast<const f32x4*>(avg.avg + i * 4), pf, avg_weight(avg));
+  *reinterpret_cast<f32x4*>(avg.avg + i * 4) = out;
+}
+
+// COEF / AVG / GUARD / MASK as in adamw_groups_kernel
+template <bool COEF, bool AVG, bool GUARD, bool MASK>
+__global__ __launch_bounds__(256) void adamw_groups_ams_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                               float* __restrict__ v, float* __restrict__ vmax, int64_t n,
+                                                               const uint8_t* __restrict__ group_of, const float* __restrict__ hyper,
+                                                               int n_groups, const int64_t* __restrict__ step,
+                                                               const float* __restrict__ coef, AvgArgs avg,
+                                                               const int32_t* __restrict__ ok) {
+  if (GUARD && !*ok) return;   // uniform over the grid: no barrier is left behind
+  __shared__ GroupScalars gs[MMFN_ADAMW_MAX_GROUPS];
+  if ((int)threadIdx.x < n_groups) gs[threadIdx.x] = ams_scalars<COEF>(hyper + threadIdx.x * 8, (double)*step, coef);
+  __syncthreads();
+  const int64_t n4 = (n + 3) >> 2;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    if (MASK && group_of[i] == MMFN_ADAMW_FROZEN) {   // frozen: none of p / m / v / vmax, p alone for the average
+      if (AVG) avg_float4(avg, i, *reinterpret_cast<const f32x4*>(p + i * 4));
+      continue;
+    }
+    f32x4 pv = adamw_ams_float4(p, g, m, v, vmax, i, gs[group_of ? group_of[i] : 0]);
+    if (AVG) {
+      asm volatile("" : "+v"(pv));   // (the new parameter is opaque to the lerp: see adamw_groups_kernel)
+      avg_float4(avg, i, pv);
+    }
+  }
+}
+
+template <bool COEF, bool AVG, bool GUARD>
+__global__ __launch_bounds__(256) void adamw_rows_ams_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                             float* __restrict__ v, float* __restrict__ vmax, int64_t n,
+                                                             const uint8_t* __restrict__ row_of, const float* __restrict__ hyper,
+                                                             AdamwRowMap rows, int n_rows, const int64_t* __restrict__ class_steps,
+                                                             const float* __restrict__ coef, AvgArgs avg,
+                                                             const int32_t* __restrict__ ok) {
+  if (GUARD && !*ok) return;
+  __shared__ GroupScalars gs[MMFN_ADAMW_MAX_ROWS];
+  if ((int)threadIdx.x < n_rows)
+    gs[threadIdx.x] = ams_scalars<COEF>(hyper + rows.group[threadIdx.x] * 8, (double)class_steps[rows.cls[threadIdx.x]], coef);
+  __syncthreads();
+  const int64_t n4 = (n + 3) >> 2;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    const int r = row_of[i];
+    if (r >= n_rows) {   // MMFN_ADAMW_FROZEN, or a byte that names no row
+      if (AVG) avg_float4(avg, i, *reinterpret_cast<const f32x4*>(p + i * 4));
+      continue;
+    }
+    f32x4 pv = adamw_ams_float4(p, g, m, v, vmax, i, gs[r]);
+    if (AVG) {
+      asm volatile("" : "+v"(pv));
+      avg_float4(avg, i, pv);
+    }
+  }
+}
+
+using AdamwGroupsAmsKernel = decltype(&adamw_groups_ams_kernel<false, false, false, false>);
+#define MMFN_ADAMW_AMS_ROW(MASK)                                                                                                \
+  adamw_groups_ams_kernel<false, false, false, MASK>, adamw_groups_ams_kernel<true, false, false, MASK>,                        \
+      adamw_groups_ams_kernel<false, true, false, MASK>, adamw_groups_ams_kernel<true, true, false, MASK>, nullptr,             \
+      adamw_groups_ams_kernel<true, false, true, MASK>, nullptr, adamw_groups_ams_kernel<true, true, true, MASK>
+const AdamwGroupsAmsKernel kAdamwGroupsAms[16] = {MMFN_ADAMW_AMS_ROW(false), MMFN_ADAMW_AMS_ROW(true)};   // as kAdamwGroups
+#undef MMFN_ADAMW_AMS_ROW
+
+using AdamwRowsAmsKernel = decltype(&adamw_rows_ams_kernel<false, false, false>);
+const AdamwRowsAmsKernel kAdamwRowsAms[8] = {   // as kAdamwRows
+    adamw_rows_ams_kernel<false, false, false>, adamw_rows_ams_kernel<true, false, false>, adamw_rows_ams_kernel<false, true, false>,
+    adamw_rows_ams_kernel<true, true, false>,   nullptr,                                    adamw_rows_ams_kernel<true, false, true>,
+    nullptr,                                    adamw_rows_ams_kernel<true, true, true>};
+
+bool vmax_ok(const float* p, const float* g, const float* m, const float* v, const float* vmax) {
+  return p && g && m && v && vmax && !((uintptr_t)vmax & 15);
+}
+}  // namespace
+
+extern "C" int mmfn_adamw_groups_ams_f32(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, const uint8_t* group_of,
+                                         const float* hyper, int n_groups, const int64_t* step, int variant, const float* coef,
+                                         float* avg, const int64_t* n_averaged, const float* ema_w, int avg_mode, const int32_t* ok,
+                                         void* stream) {
+  if (n <= 0) return 0;
+  if (variant < 0 || variant >= 16 || !kAdamwGroupsAms[variant]) return MMFN_EINVAL;
+  const bool with_coef = variant & MMFN_ADAMW_COEF, with_avg = variant & MMFN_ADAMW_AVG, guard = variant & MMFN_ADAMW_GUARD;
+  const bool mask = variant & MMFN_ADAMW_MASK;
+  const AvgArgs a = with_avg ? AvgArgs{avg, n_averaged, ema_w, avg_mode} : AvgArgs{};
+  if (!vmax_ok(p, g, m, v, vmax) || ((uintptr_t)step & 7) || !adamw_args_ok(p, g, m, v, n, hyper, n_groups, step) ||
+      (with_coef && !coef) || (with_avg && !avg_args_ok(a)) || (guard && !flag_ok(ok)) || (mask && !group_of))
+    return MMFN_EINVAL;
+  hipLaunchKernelGGL(kAdamwGroupsAms[variant], dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, vmax, n, group_of,
+                     hyper, n_groups, step, with_coef ? coef : nullptr, a, guard ? ok : nullptr);
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mmfn_adamw_rows_ams_f32(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, const uint8_t* row_of,
+                                       const float* hyper, int n_groups, const int32_t* rows, int n_rows, const int64_t* class_steps,
+                                       int n_classes, int variant, const float* coef, float* avg, const int64_t* n_averaged,
+                                       const float* ema_w, int avg_mode, const int32_t* ok, void* stream) {
+  if (n <= 0) return 0;
+  if (variant < 0 || variant >= 8 || !kAdamwRowsAms[variant]) return MMFN_EINVAL;
+  const bool with_coef = variant & MMFN_ADAMW_COEF, with_avg = variant & MMFN_ADAMW_AVG, guard = variant & MMFN_ADAMW_GUARD;
+  const AvgArgs a = with_avg ? AvgArgs{avg, n_averaged, ema_w, avg_mode} : AvgArgs{};
+  if (!vmax_ok(p, g, m, v, vmax) || !row_of || !rows || n_rows < 1 || n_rows > MMFN_ADAMW_MAX_ROWS || n_classes < 1 ||
+      n_classes > 65536 || ((uintptr_t)class_steps & 7) || !adamw_args_ok(p, g, m, v, n, hyper, n_groups, class_steps) ||
+      (with_coef && !coef) || (with_avg && !avg_args_ok(a)) || (guard && !flag_ok(ok)))
+    return MMFN_EINVAL;
+  AdamwRowMap map{};
+  for (int r = 0; r < n_rows; ++r) {   // rows: HOST memory, [n_rows][2] = (group, class), every entry inside its table
+    const int32_t grp = rows[2 * r], cls = rows[2 * r + 1];
+    if (grp < 0 || grp >= n_groups || cls < 0 || cls >= n_classes) return MMFN_EINVAL;
+    map.group[r] = (uint8_t)grp;
+    map.cls[r] = (uint16_t)cls;
+  }
+  hipLaunchKernelGGL(kAdamwRowsAms[variant], dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, vmax, n, row_of,
+                     hyper, map, n_rows, class_steps, with_coef ? coef : nullptr, a, guard ? ok : nullptr);
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mmfn_adamw_max_blocks(void) { return kAdamwMaxBlocks; }
 
 extern "C" int mmfn_class_steps_advance(int64_t* class_steps, const uint8_t* active, int n_classes, const int32_t* ok, void* stream) {
   if (!class_steps || ((uintptr_t)class_steps & 7) || !active || n_classes < 1 || n_classes > 65536 || ((uintptr_t)ok & 3))

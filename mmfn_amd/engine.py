@@ -1464,6 +1464,8 @@ class Engine(object):
         self.opt_hyper = torch.zeros(16, 8, dtype=torch.float32, device=dev)
         self._hyper_host = None
         self._hyper_pinned, self._hyper_slot = None, 0
+        self.opt_amsgrad = ()       # per optimizer group: amsgrad (set_amsgrad); the flags travel in the last column of opt_hyper
+        self._hyper_flags = ()      # ... as set_hyper last wrote them: the AdamW launch follows the table
         # gradient accumulation (accumulate_step) and global-norm clipping: allocated on first use only
         self.grad_acc = None        # fp32 [0, tail): the sum of the pending micro-steps' gradients
         self.accum_pending = 0      # micro-steps in grad_acc (host count: it picks the 1 / (k * world) of the final step)
@@ -2056,12 +2058,36 @@ class Engine(object):
         (optim.FusedAdamW builds it from torch-style param_groups), or None = one group."""
         self.opt_group_of = group_of
 
+    def set_amsgrad(self, flags):
+        """flags: one bool per optimizer group, torch.optim.AdamW's amsgrad (optim.FusedAdamW hands them over beside its hyper
+        rows).  The first set flag allocates layout.max_exp_avg_sq (zeros, a fifth flat buffer); with none set nothing is
+        allocated and every step issues the launches it always issued.  The flags reach the kernel through the last column of
+        the hyper table (set_hyper).  Steps with a set flag run eagerly: parallel.GraphedStep refuses to capture them, and to
+        replay a step captured before a flag was set."""
+        flags = tuple(bool(f) for f in flags)
+        if flags == self.opt_amsgrad:
+            return
+        if len(flags) > 16:
+            raise ValueError("at most 16 optimizer groups")
+        if any(flags) and self.layout.max_exp_avg_sq is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("max_exp_avg_sq must be allocated before a hipGraph capture: call Engine.set_amsgrad() before it")
+            self.layout.ensure_max_exp_avg_sq()
+        self.opt_amsgrad = flags
+
+    def amsgrad_flags(self, n_groups):
+        """The amsgrad flags of a step with n_groups hyper rows (a group without a flag has none; a step with one row runs
+        everything as group 0, as in _group_table)."""
+        f = self.opt_amsgrad[:n_groups]
+        return f + (False,) * (n_groups - len(f))
+
     def set_hyper(self, rows):
         """rows: [(lr, beta1, beta2, eps, weight_decay, grad_scale), ...] one per optimizer group.  They live in a small
         device table read by the AdamW kernel, so a learning-rate schedule changes the table (one tiny host-to-device copy,
         outside any captured graph) instead of invalidating captured hipGraphs."""
         rows = tuple(tuple(float(x) for x in r) for r in rows)
-        if rows == self._hyper_host:
+        flags = self.amsgrad_flags(len(rows))
+        if rows == self._hyper_host and flags == self._hyper_flags:
             return
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("optimizer hyper-parameters changed inside a hipGraph capture; call Engine.set_hyper() before it")
@@ -2079,11 +2105,13 @@ class Engine(object):
         host.zero_()
         for i, r in enumerate(rows):
             host[i, :len(r)] = torch.tensor(r, dtype=torch.float32)   # (a 7th column: max_norm of a clipped step)
+            host[i, 7] = 1.0 if flags[i] else 0.0                      # (the 8th: the group's amsgrad flag)
         self.opt_hyper.copy_(host, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
         self._hyper_events[slot] = ev
         self._hyper_host = rows
+        self._hyper_flags = flags
 
     @staticmethod
     def hyper_rows(lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0, groups=None):
@@ -2124,18 +2152,20 @@ class Engine(object):
         the non-finite guard's flag, every one of them behind it."""
         L, a = self.layout, self.average
         avg = None if a is None else (a.module._layout.params, a.n_averaged, a.ema_weight, a.mode_code)
+        # amsgrad in some group of the table as set_hyper wrote it: the launch that also carries max_exp_avg_sq (None: the plain one)
+        vmax = L.max_exp_avg_sq if any(self._hyper_flags[:n_groups]) else None
         if not self.classes.uniform():
             # a tensor that steps has a count of its own: the instance whose bias corrections follow the step classes
             row_of, rows = self._rows(n_groups)
             ops.adamw_rows(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self._class_steps, self.classes.n_classes, self.opt_hyper,
-                           n_groups, row_of, rows, n=L.tail, coef=coef, avg=avg, ok=ok)
+                           n_groups, row_of, rows, n=L.tail, coef=coef, avg=avg, ok=ok, vmax=vmax)
         elif self.frozen:
             # the masked instance: frozen float4s keep parameter, moments and decay untouched (the average still follows them)
             ops.adamw_groups(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self.step_count, self.opt_hyper, n_groups,
-                             group_of=self._group_table(n_groups), n=L.tail, coef=coef, avg=avg, ok=ok, mask=True)
+                             group_of=self._group_table(n_groups), n=L.tail, coef=coef, avg=avg, ok=ok, mask=True, vmax=vmax)
         else:
             ops.adamw_groups(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self.step_count, self.opt_hyper, n_groups,
-                             group_of=self.opt_group_of if n_groups > 1 else None, n=L.tail, coef=coef, avg=avg, ok=ok)
+                             group_of=self.opt_group_of if n_groups > 1 else None, n=L.tail, coef=coef, avg=avg, ok=ok, vmax=vmax)
         self.never_stepped = self.frozen if self.never_stepped is None else (self.never_stepped & self.frozen)
         self.classes.launched()
         if a is not None:

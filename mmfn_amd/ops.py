@@ -1189,12 +1189,23 @@ ADAMW_COEF, ADAMW_AVG, ADAMW_GUARD, ADAMW_MASK = 1, 2, 4, 8   # mirror include/m
 ADAMW_FROZEN = 255   # group_of byte of a float4 that belongs to a frozen parameter (ADAMW_MASK)
 
 
-def adamw_groups(p, g, m, v, step, hyper, n_groups, group_of=None, n=None, coef=None, avg=None, ok=None, mask=False):
+def adamw_max_blocks():
+    """The grid cap of the grouped / rows AdamW launches: beyond 1024 * this many floats their grid-stride loops go round again."""
+    return int(lib().mmfn_adamw_max_blocks())
+
+
+def _check_vmax(vmax, p, n):
+    if vmax.dtype != torch.float32 or vmax.device != p.device or vmax.numel() < n:
+        raise ValueError("vmax (max_exp_avg_sq) is a float32 tensor on the parameters' device with one entry per parameter of the range")
+
+
+def adamw_groups(p, g, m, v, step, hyper, n_groups, group_of=None, n=None, coef=None, avg=None, ok=None, mask=False, vmax=None):
     """AdamW with the hyper-parameter rows (and optional per-float4 group ids) in device memory.  coef: a device scalar that
     multiplies every group's grad_scale (the clip coefficient).  avg: (avg, n_averaged, ema_weight, mode), every new parameter is
     also folded into avg[0, n) as weight_average does.  ok (with coef): the non-finite guard's device flag (int32), the launch
     touches nothing when it is 0.  mask: float4s whose group_of byte is ADAMW_FROZEN keep p / m / v untouched (an average is still
-    updated from p); group_of is then mandatory, also with one group."""
+    updated from p); group_of is then mandatory, also with one group.  vmax: the amsgrad launch (mmfn_adamw_groups_ams_f32) - the
+    running maximum of v, read and written for the groups whose hyper row has a non-zero last float; None: the launch without."""
     n = p.numel() if n is None else n
     if mask and (group_of is None or group_of.dtype != torch.uint8 or group_of.numel() * 4 < n):
         raise ValueError("the masked AdamW launch needs a uint8 group table with one byte per float4 of the range")
@@ -1206,6 +1217,11 @@ def adamw_groups(p, g, m, v, step, hyper, n_groups, group_of=None, n=None, coef=
     variant = sum(bit for bit, arg in ((ADAMW_COEF, coef), (ADAMW_AVG, avg), (ADAMW_GUARD, ok)) if arg is not None)
     if mask:
         variant |= ADAMW_MASK
+    if vmax is not None:
+        _check_vmax(vmax, p, n)
+        _call("mmfn_adamw_groups_ams_f32", ptr(p), ptr(g), ptr(m), ptr(v), ptr(vmax), n, ptr(group_of), ptr(hyper), n_groups, ptr(step),
+              variant, ptr(coef), ptr(a), ptr(n_averaged), ptr(ema_weight), int(mode), ptr(ok), stream())
+        return
     _call("mmfn_adamw_groups_f32", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(group_of), ptr(hyper), n_groups, ptr(step), variant,
           ptr(coef), ptr(a), ptr(n_averaged), ptr(ema_weight), int(mode), ptr(ok), stream())
 
@@ -1213,10 +1229,10 @@ def adamw_groups(p, g, m, v, step, hyper, n_groups, group_of=None, n=None, coef=
 ADAMW_MAX_ROWS = 254   # mirror include/mmfn_hip.h
 
 
-def adamw_rows(p, g, m, v, class_steps, n_classes, hyper, n_groups, row_of, rows, n=None, coef=None, avg=None, ok=None):
+def adamw_rows(p, g, m, v, class_steps, n_classes, hyper, n_groups, row_of, rows, n=None, coef=None, avg=None, ok=None, vmax=None):
     """AdamW with per-tensor step counts: row_of (uint8, one byte per float4, ADAMW_FROZEN over frozen float4s) selects a row of
     `rows` (a CPU int32 tensor [n_rows, 2] of (hyper group, step class)); a row's bias corrections come from class_steps[class]
-    (int64, device).  coef / avg / ok as in adamw_groups; frozen float4s as in its masked launch."""
+    (int64, device).  coef / avg / ok / vmax as in adamw_groups; frozen float4s as in its masked launch."""
     n = p.numel() if n is None else n
     if row_of is None or row_of.dtype != torch.uint8 or row_of.numel() * 4 < n:
         raise ValueError("the AdamW launch with step classes needs a uint8 row table with one byte per float4 of the range")
@@ -1232,6 +1248,12 @@ def adamw_rows(p, g, m, v, class_steps, n_classes, hyper, n_groups, row_of, rows
     if ok is not None and coef is None:
         raise ValueError("the guarded AdamW launch is the coefficient instance: pass coef")
     variant = sum(bit for bit, arg in ((ADAMW_COEF, coef), (ADAMW_AVG, avg), (ADAMW_GUARD, ok)) if arg is not None)
+    if vmax is not None:
+        _check_vmax(vmax, p, n)
+        _call("mmfn_adamw_rows_ams_f32", ptr(p), ptr(g), ptr(m), ptr(v), ptr(vmax), n, ptr(row_of), ptr(hyper), n_groups, rows.data_ptr(),
+              rows.shape[0], ptr(class_steps), n_classes, variant, ptr(coef), ptr(a), ptr(n_averaged), ptr(ema_weight), int(mode),
+              ptr(ok), stream())
+        return
     _call("mmfn_adamw_rows_f32", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(row_of), ptr(hyper), n_groups, rows.data_ptr(), rows.shape[0],
           ptr(class_steps), n_classes, variant, ptr(coef), ptr(a), ptr(n_averaged), ptr(ema_weight), int(mode), ptr(ok), stream())
 

@@ -14,6 +14,10 @@ Parameter groups: the reference also defines (and never uses) a decay / no-decay
 network; `FusedAdamW(model, param_groups=...)` takes such torch-style groups, each with its own lr / betas / eps /
 weight_decay.  All hyper-parameters live in a small device table the kernel reads (Engine.set_hyper), so changing the
 learning rate between steps costs one 512-byte copy and never re-captures a hipGraph.
+
+amsgrad: `FusedAdamW(model, amsgrad=True)`, or "amsgrad" in a group dict, as in torch.optim.AdamW.  The running maximum
+`max_exp_avg_sq` is a fifth flat buffer (FlatLayout.max_exp_avg_sq, allocated only when some group asks for it), updated inside
+the same AdamW launch (mmfn_adamw_groups_ams_f32 / mmfn_adamw_rows_ams_f32); the state dict carries it in checkpoint shape.
 """
 import torch
 import torch.nn as nn
@@ -45,9 +49,9 @@ def configure_optimizers(model, weight_decay=0.01):
 
 
 class FusedAdamW(object):
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, param_groups=None):
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, param_groups=None, amsgrad=False):
         self.model = model
-        self.defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False)
+        self.defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=bool(amsgrad))
         if param_groups is None:
             param_groups = [{"params": list(model.parameters())}]
         self.param_groups = []
@@ -55,6 +59,7 @@ class FusedAdamW(object):
             full = dict(self.defaults)
             full.update({k: v for k, v in g.items() if k != "params"})
             full["betas"] = tuple(full["betas"])
+            full["amsgrad"] = bool(full["amsgrad"])
             full["params"] = list(g["params"])
             self.param_groups.append(full)
         by_id = {id(p): n for n, p in model.named_parameters()}
@@ -108,6 +113,21 @@ class FusedAdamW(object):
             self._group_of = gid.to(L.device)
         if L.device.type == "cuda":
             self.model._engine_for().set_param_groups(self._group_of)
+        self.sync_amsgrad()
+
+    def amsgrad_flags(self):
+        """(amsgrad,) per group - what Engine.set_amsgrad takes, beside hyper_rows()."""
+        return tuple(bool(g.get("amsgrad", False)) for g in self.param_groups)
+
+    def sync_amsgrad(self):
+        """The groups' amsgrad flags as they stand (torch lets a caller assign param_groups[i]["amsgrad"]) reach the engine, and
+        max_exp_avg_sq exists once a group asks for it: at construction, in front of every step and after load_state_dict."""
+        flags = self.amsgrad_flags()
+        L = self.model._layout
+        if L.device.type == "cuda":
+            self.model._engine_for().set_amsgrad(flags)
+        elif any(flags):
+            L.ensure_max_exp_avg_sq()
 
     # ------------------------------------------------------------------ stepping
     @property
@@ -117,6 +137,7 @@ class FusedAdamW(object):
     def hyper_rows(self):
         """[(lr, beta1, beta2, eps, weight_decay)] per group - what Engine.optimizer_step(groups=...) takes."""
         self._check_ungrouped()
+        self.sync_amsgrad()   # (the flags travel beside the rows: the engine writes them into the same device table)
         return [(g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"]) for g in self.param_groups]
 
     def zero_grad(self, set_to_none=True):
@@ -129,11 +150,12 @@ class FusedAdamW(object):
 
     # ------------------------------------------------------------------ torch.optim.AdamW-format state
     def _moment_views(self):
-        """(name, exp_avg view, exp_avg_sq view) in torch's parameter-id order: group by group."""
+        """(name, exp_avg view, exp_avg_sq view, max_exp_avg_sq view or None, group index) in torch's parameter-id order: group
+        by group."""
         L = self.model._layout
         named = dict(self.model.named_parameters())
         out = []
-        for names in self._group_names:
+        for gi, names in enumerate(self._group_names):
             for name in names:
                 off, n = L.offsets[name]
                 p = named[name]
@@ -142,7 +164,7 @@ class FusedAdamW(object):
                     view = lambda flat, off=off, n=n, o=o, i=i, kh=kh, kw=kw: flat[off:off + n].view(o, kh, kw, i).permute(0, 3, 1, 2)
                 else:
                     view = lambda flat, off=off, n=n, shp=p.shape: flat[off:off + n].view(shp)
-                out.append((name, view(L.exp_avg), view(L.exp_avg_sq)))
+                out.append((name, view(L.exp_avg), view(L.exp_avg_sq), None if L.max_exp_avg_sq is None else view(L.max_exp_avg_sq), gi))
         return out
 
     def _engine(self):
@@ -160,11 +182,14 @@ class FusedAdamW(object):
         steps = self.tensor_steps()
         state = {}
         # a tensor that never took a step (frozen at every optimizer step so far, or no step yet): torch holds no state for it either
-        for idx, (name, m, v) in enumerate(self._moment_views()):
+        self.sync_amsgrad()
+        for idx, (name, m, v, vmax, gi) in enumerate(self._moment_views()):
             if name in L.unused or steps[name] == 0:
                 continue
             state[idx] = {"step": torch.tensor(float(steps[name])), "exp_avg": m.clone().contiguous(),
                           "exp_avg_sq": v.clone().contiguous()}
+            if self.param_groups[gi]["amsgrad"]:   # torch keeps max_exp_avg_sq for the parameters of an amsgrad group only
+                state[idx]["max_exp_avg_sq"] = vmax.clone().contiguous()
         groups = []
         start = 0
         for g, names in zip(self.param_groups, self._group_names):
@@ -177,28 +202,45 @@ class FusedAdamW(object):
 
     def load_state_dict(self, sd):
         """Per-parameter `step` values may differ (a torch run that unfroze tensors late): every tensor keeps its own count.  An
-        id without an entry has count 0 and zero moments; a trained tensor outside this optimizer's groups likewise."""
+        id without an entry has count 0 and zero moments; a trained tensor outside this optimizer's groups likewise.  amsgrad comes
+        from the checkpoint's groups, as torch takes its groups from the checkpoint: max_exp_avg_sq is filled from the entries of
+        the amsgrad groups (zero elsewhere); an entry of such a group without it is a ValueError."""
         L = self.model._layout
         eng = self._engine()
         if len(sd["param_groups"]) != len(self.param_groups):
             raise ValueError("optimizer state has %d parameter groups, this optimizer %d" % (len(sd["param_groups"]), len(self.param_groups)))
-        for mine, names, theirs in zip(self.param_groups, self._group_names, sd["param_groups"]):
+        get = lambda idx: sd["state"].get(idx, sd["state"].get(str(idx)))
+        start = 0
+        for names, theirs in zip(self._group_names, sd["param_groups"]):   # (checked before anything is changed)
             if len(theirs["params"]) != len(names):
                 raise ValueError("optimizer state holds %d parameters in a group, the model has %d" % (len(theirs["params"]), len(names)))
+            if theirs.get("amsgrad", False):
+                for idx in range(start, start + len(names)):
+                    if get(idx) is not None and "max_exp_avg_sq" not in get(idx):
+                        raise ValueError("optimizer state: parameter %d (%s) belongs to a group with amsgrad=True but its entry holds "
+                                         "no max_exp_avg_sq" % (idx, names[idx - start]))
+            start += len(names)
+        for mine, theirs in zip(self.param_groups, sd["param_groups"]):
             for k in _HYPER:
                 if k in theirs:
                     mine[k] = tuple(theirs[k]) if k == "betas" else theirs[k]
+            mine["amsgrad"] = bool(theirs.get("amsgrad", False))
+        self.sync_amsgrad()
         steps = {}
         absent = set()
         L.exp_avg.zero_()
         L.exp_avg_sq.zero_()
-        for idx, (name, m, v) in enumerate(self._moment_views()):
-            st = sd["state"].get(idx, sd["state"].get(str(idx)))
+        if L.max_exp_avg_sq is not None:
+            L.max_exp_avg_sq.zero_()
+        for idx, (name, m, v, vmax, gi) in enumerate(self._moment_views()):
+            st = get(idx)
             if st is None:
                 absent.add(name)
                 continue
             m.copy_(st["exp_avg"])
             v.copy_(st["exp_avg_sq"])
+            if self.param_groups[gi]["amsgrad"]:
+                vmax.copy_(st["max_exp_avg_sq"])
             steps[name] = int(float(st["step"]))
         vec = [steps.get(n, 0) for n in L.step_classes.names]
         top = max(vec) if vec else 0

@@ -85,6 +85,12 @@ class DataParallel(object):
         # optimizer moments + step counter too, so a run resumed on rank 0 continues identically everywhere
         self.dist.broadcast(L.exp_avg, src)
         self.dist.broadcast(L.exp_avg_sq, src)
+        # amsgrad: the running maximum travels with the moments.  Whether rank `src` holds one goes first (a checkpoint may have
+        # switched amsgrad on there alone), so that every rank issues the same collectives
+        has = torch.tensor([int(L.max_exp_avg_sq is not None)], dtype=torch.int64, device=L.device)
+        self.dist.broadcast(has, src)
+        if int(has.item()):
+            self.dist.broadcast(L.ensure_max_exp_avg_sq(), src)
         if L.device.type == "cuda":  # (the CPU unit tests exercise the bucket logic without an engine)
             eng = self.module._engine_for()
             self.dist.broadcast(eng.step_count, src)
@@ -284,6 +290,9 @@ class GraphedStep(object):
     Frozen parameters (Engine.trainable_mask): the capture holds the backward pruned for the requires_grad flags of that moment and
     the AdamW launch masked for them; a replay after the flags changed raises, like the checks below.
 
+    amsgrad (Engine.set_amsgrad): an optimizer step with amsgrad in some group is not captured yet - the capture is refused, and
+    so is the replay of a step captured before amsgrad was switched on; such steps run eagerly (Engine.train_step).
+
     Non-finite guard (Engine.set_nonfinite_guard): a "final" step captured while it is armed holds the guarded launches (the norm
     is always measured, max_norm = inf without clip_grad_norm) and replays only while it stays armed; the BatchNorm snapshot of
     a group's first micro-step is issued by __call__ in front of the replay, outside the capture.  The "step" shorthand says
@@ -299,6 +308,8 @@ class GraphedStep(object):
             raise ValueError("a micro-step issues no collective: capture it without dp")
         if variant == "step" and engine.nonfinite_guard:
             raise ValueError('the non-finite guard is armed: capture the optimizer step as variant="final", fold=False')
+        if variant != "micro" and any(engine.opt_amsgrad):
+            raise RuntimeError("amsgrad is on in an optimizer group: amsgrad steps are not captured, run them eagerly (Engine.train_step)")
         self.engine, self.dp = engine, dp
         if variant == "step":
             clip_grad_norm, fold = None, False
@@ -413,6 +424,8 @@ class GraphedStep(object):
         if self.variant != "micro" and eng.classes.epoch != self.class_epoch:
             raise RuntimeError("this step was captured for other per-tensor step counts (Engine.set_tensor_steps, a loaded optimizer "
                                "state): capture the step again")
+        if self.variant != "micro" and any(eng.opt_amsgrad):
+            raise RuntimeError("amsgrad was switched on after this step was captured: amsgrad steps run eagerly (Engine.set_amsgrad)")
         if self.variant != "micro" and eng.nonfinite_guard != self.guard:
             raise RuntimeError("this step was captured with the non-finite guard %s; the engine now has it %s: capture the step again"
                                % (("armed", "disarmed") if self.guard else ("disarmed", "armed")))

@@ -212,6 +212,7 @@ class FlatLayout(object):
         self.step_classes = StepClasses([n for n in self.offsets if n not in unused])   # per-tensor AdamW step counts
         self.device = None
         self.params = self.grads = self.exp_avg = self.exp_avg_sq = None
+        self.max_exp_avg_sq = None   # amsgrad's running maximum of exp_avg_sq: allocated when a group first asks for it (ensure_max_exp_avg_sq)
         self.buffers_flat = None
 
     @staticmethod
@@ -316,9 +317,18 @@ class FlatLayout(object):
         self.params, self.grads = params, grads
         self.exp_avg = torch.zeros_like(params)
         self.exp_avg_sq = torch.zeros_like(params)
+        if self.max_exp_avg_sq is not None:
+            self.max_exp_avg_sq = torch.zeros_like(params)
         self.buffers_flat, self.counters_flat = fflat, iflat
         self.device = device
         return self
+
+    def ensure_max_exp_avg_sq(self):
+        """The fifth flat buffer, torch.optim.AdamW's max_exp_avg_sq (amsgrad): zeros, allocated the first time an optimizer group
+        asks for amsgrad, so a run without it holds four buffers as before."""
+        if self.max_exp_avg_sq is None:
+            self.max_exp_avg_sq = torch.zeros_like(self.params)
+        return self.max_exp_avg_sq
 
     # ------------------------------------------------------------------ bf16 weight shadows (bf16 training mode)
     def make_shadows(self):

@@ -213,7 +213,7 @@ class Trainer(object):
         def run():   # the eager step
             return eng.train_step(inp, gt, lr=lr, dp=dp, clip_grad_norm=clip, **adam) if final else eng.accumulate_step(inp, gt)
 
-        if not graph:
+        if not graph or any(eng.opt_amsgrad):   # (amsgrad steps are not captured: parallel.GraphedStep)
             return run()
         variant = "final" if final else "micro"
         with eng.mask_held() as mask:   # one read of the flags for the signature and the step
@@ -459,14 +459,15 @@ def _hyper_rows(optimizer):
 
 def sync_resume_state(trainer, optimizer, dist, src=0):
     """After rank `src` resumed from disk: every rank takes its epoch / iteration counters, loss history and the
-    optimizer hyper-parameters (lr, betas, eps, weight decay per group).  Without this the ranks would iterate different
+    optimizer hyper-parameters (lr, betas, eps, weight decay and the amsgrad flag per group).  Without this the ranks would iterate different
     epoch ranges (and deadlock in the gradient all-reduce when rank 0 leaves the loop first), seed their samplers
     differently and step with different learning rates.  Weights / moments / step counter travel separately
     (DataParallel.broadcast_parameters)."""
     payload = [None]
     if dist.get_rank() == src:
         payload[0] = {"table": trainer._log_table(),
-                      "groups": [{k: g[k] for k in ("lr", "betas", "eps", "weight_decay")} for g in optimizer.param_groups]}
+                      "groups": [dict({k: g[k] for k in ("lr", "betas", "eps", "weight_decay")}, amsgrad=bool(g.get("amsgrad", False)))
+                                 for g in optimizer.param_groups]}
     dist.broadcast_object_list(payload, src=src)
     st = payload[0]
     t = st["table"]
@@ -477,6 +478,9 @@ def sync_resume_state(trainer, optimizer, dist, src=0):
         raise ValueError("rank %d has %d optimizer groups, rank %d has %d" % (dist.get_rank(), len(optimizer.param_groups), src, len(st["groups"])))
     for g, new in zip(optimizer.param_groups, st["groups"]):
         g["lr"], g["betas"], g["eps"], g["weight_decay"] = new["lr"], tuple(new["betas"]), new["eps"], new["weight_decay"]
+        g["amsgrad"] = new["amsgrad"]
+    if hasattr(optimizer, "sync_amsgrad"):   # (FusedAdamW: the flags reach the engine, which allocates max_exp_avg_sq if need be)
+        optimizer.sync_amsgrad()
 
 
 def _plain_state_dict(model):
