@@ -582,6 +582,24 @@ int mmfn_adamw_rows_ams_f32(float* p, const float* g, float* m, float* v, float*
                             const float* hyper, int n_groups, const int32_t* rows, int n_rows, const int64_t* class_steps,
                             int n_classes, int variant, const float* coef, float* avg, const int64_t* n_averaged, const float* ema_w,
                             int avg_mode, const int32_t* ok, void* stream);
+/* Momentum SGD (torch.optim.SGD, the single-tensor form) on the conventions of mmfn_adamw_groups_f32 / mmfn_adamw_rows_f32: the
+ * same variant bits, checks, grid, group / row bytes, step counters, clip coefficient, guard flag and in-launch average.  buf (n
+ * floats, 16-byte aligned, never NULL) is torch's momentum_buffer, the only state stream.
+ * hyper row: {lr, momentum, dampening, nesterov (0 / 1), weight_decay, grad_scale, max_norm, 0}.  Per element
+ *     gg  = g * grad_scale                      (grad_scale * *coef with COEF)
+ *     d   = gg + weight_decay * p               (coupled decay)
+ *     buf = first ? d : momentum * buf + (1 - dampening) * d
+ *     p   = p - lr * (nesterov ? d + momentum * buf : buf)
+ * first: the step count the float4 reads is 1 (*step for the groups entry point, class_steps[class of row] for the rows one; the
+ * caller advances it before the launch), torch's `momentum_buffer is None`.  A float4 of a group with momentum 0 neither loads
+ * nor stores buf.  A frozen float4 touches neither p nor buf (p alone with AVG); a GUARD instance with *ok == 0 touches nothing.
+ * 20 B per parameter, 12 B in a group with momentum 0. */
+int mmfn_sgd_groups_f32(float* p, const float* g, float* buf, int64_t n, const uint8_t* group_of, const float* hyper, int n_groups,
+                        const int64_t* step, int variant, const float* coef, float* avg, const int64_t* n_averaged,
+                        const float* ema_w, int avg_mode, const int32_t* ok, void* stream);
+int mmfn_sgd_rows_f32(float* p, const float* g, float* buf, int64_t n, const uint8_t* row_of, const float* hyper, int n_groups,
+                      const int32_t* rows, int n_rows, const int64_t* class_steps, int n_classes, int variant, const float* coef,
+                      float* avg, const int64_t* n_averaged, const float* ema_w, int avg_mode, const int32_t* ok, void* stream);
 /* the cap of the grid of the grouped / rows AdamW launches (256 threads, one float4 each): a range of more than 1024 * this many
  * floats goes round their grid-stride loops again */
 int mmfn_adamw_max_blocks(void);

@@ -3,6 +3,8 @@
 // HBM-bound: 28 B/param (read p,g,m,v; write p,m,v) in one pass with 16-byte accesses.
 // The step count lives in device memory so the launch is hipGraph-replayable.  Per-tensor step counts (a tensor unfrozen late
 // starts its bias correction at 1, as torch.optim.AdamW's state[p]["step"]): one counter per step class, adamw_rows_kernel below.
+// Momentum SGD (torch.optim.SGD) is a second update rule on the same buffers, tables and counters: sgd_groups_kernel /
+// sgd_rows_kernel, 20 B/param with the momentum buffer in the place of the first moment.
 #include <algorithm>
 
 #include "common.h"
@@ -527,6 +529,163 @@ extern "C" int mmfn_adamw_rows_ams_f32(float* p, const float* g, float* m, float
   }
   hipLaunchKernelGGL(kAdamwRowsAms[variant], dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, vmax, n, row_of,
                      hyper, map, n_rows, class_steps, with_coef ? coef : nullptr, a, guard ? ok : nullptr);
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- momentum SGD (torch.optim.SGD, the single-tensor form) on the machinery of the grouped AdamW launches -------------------
+// One state stream buf (torch's momentum_buffer) instead of m and v: 20 B per parameter (read p, g, buf; write p, buf), 12 B for a
+// float4 of a group with momentum 0, which neither loads nor stores buf.  hyper row: {lr, momentum, dampening, nesterov,
+// weight_decay, grad_scale, max_norm, 0}.  Per element
+//     d   = g * grad_scale + weight_decay * p          (coupled decay)
+//     buf = first ? d : momentum * buf + (1 - dampening) * d
+//     p   = p - lr * (nesterov ? d + momentum * buf : buf)
+// first: the tensor's step count after the advance is 1 (torch: momentum_buffer is None) - *step for the groups kernel, the
+// row's class counter for the rows kernel.  Kernels of their own: the AdamW launches keep their code.
+namespace {
+struct SgdScalars { float lr, momentum, omd, wd, grad_scale, nesterov, first, pad; };
+
+template <bool COEF>
+__device__ inline SgdScalars sgd_scalars(const float* __restrict__ h, int64_t t, const float* __restrict__ coef) {
+  SgdScalars s;
+  s.lr = h[0]; s.momentum = h[1];
+  s.omd = (float)(1.0 - (double)h[2]);   // in fp64 like torch's Python-side 1 - dampening, rounded once
+  s.wd = h[4]; s.grad_scale = COEF ? h[5] * *coef : h[5];
+  s.nesterov = h[3]; s.first = t == 1 ? 1.f : 0.f; s.pad = 0.f;
+  return s;
+}
+
+// One float4 of the step; returns the new parameter.  Written operation by operation with explicit fmaf calls and contraction
+// switched off for the rest (as adamw_ams_float4), so that the bits do not depend on the instance around it.
+__device__ inline f32x4 sgd_float4(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, int64_t i,
+                                   const SgdScalars& s) {
+#pragma clang fp contract(off)
+  const bool mom = s.momentum != 0.f, first = s.first != 0.f, nesterov = s.nesterov != 0.f, decay = s.wd != 0.f;
+  f32x4 pv = *reinterpret_cast<f32x4*>(p + i * 4);
+  const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i * 4);
+  f32x4 bv = {0.f, 0.f, 0.f, 0.f};
+  if (mom && !first) bv = *reinterpret_cast<f32x4*>(buf + i * 4);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float gg = gv[e] * s.grad_scale;
+    const float d = decay ? __builtin_fmaf(s.wd, pv[e], gg) : gg;
+    float u = d;
+    if (mom) {
+      bv[e] = first ? d : __builtin_fmaf(s.omd, d, s.momentum * bv[e]);
+      u = nesterov ? __builtin_fmaf(s.momentum, bv[e], d) : bv[e];
+    }
+    pv[e] = __builtin_fmaf(-s.lr, u, pv[e]);
+  }
+  *reinterpret_cast<f32x4*>(p + i * 4) = pv;
+  if (mom) *reinterpret_cast<f32x4*>(buf + i * 4) = bv;
+  return pv;
+}
+
+// COEF / AVG / GUARD / MASK as in adamw_groups_kernel
+template <bool COEF, bool AVG, bool GUARD, bool MASK>
+__global__ __launch_bounds__(256) void sgd_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                         int64_t n, const uint8_t* __restrict__ group_of,
+                                                         const float* __restrict__ hyper, int n_groups,
+                                                         const int64_t* __restrict__ step, const float* __restrict__ coef, AvgArgs avg,
+                                                         const int32_t* __restrict__ ok) {
+  if (GUARD && !*ok) return;   // uniform over the grid: no barrier is left behind
+  __shared__ SgdScalars gs[MMFN_ADAMW_MAX_GROUPS];
+  if ((int)threadIdx.x < n_groups) gs[threadIdx.x] = sgd_scalars<COEF>(hyper + threadIdx.x * 8, *step, coef);
+  __syncthreads();
+  const int64_t n4 = (n + 3) >> 2;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    if (MASK && group_of[i] == MMFN_ADAMW_FROZEN) {   // frozen: neither p nor buf, p alone for the average
+      if (AVG) avg_float4(avg, i, *reinterpret_cast<const f32x4*>(p + i * 4));
+      continue;
+    }
+    // (a byte that names no group of the table reads group 0: it never indexes past the scalars in LDS)
+    const int grp = group_of ? group_of[i] : 0;
+    f32x4 pv = sgd_float4(p, g, buf, i, gs[grp < n_groups ? grp : 0]);
+    if (AVG) {
+      asm volatile("" : "+v"(pv));   // (the new parameter is opaque to the lerp: see adamw_groups_kernel)
+      avg_float4(avg, i, pv);
+    }
+  }
+}
+
+template <bool COEF, bool AVG, bool GUARD>
+__global__ __launch_bounds__(256) void sgd_rows_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                       int64_t n, const uint8_t* __restrict__ row_of, const float* __restrict__ hyper,
+                                                       AdamwRowMap rows, int n_rows, const int64_t* __restrict__ class_steps,
+                                                       const float* __restrict__ coef, AvgArgs avg, const int32_t* __restrict__ ok) {
+  if (GUARD && !*ok) return;
+  __shared__ SgdScalars gs[MMFN_ADAMW_MAX_ROWS];   // 254 * 32 B = 8128 B
+  if ((int)threadIdx.x < n_rows)
+    gs[threadIdx.x] = sgd_scalars<COEF>(hyper + rows.group[threadIdx.x] * 8, class_steps[rows.cls[threadIdx.x]], coef);
+  __syncthreads();
+  const int64_t n4 = (n + 3) >> 2;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    const int r = row_of[i];
+    if (r >= n_rows) {   // MMFN_ADAMW_FROZEN, or a byte that names no row
+      if (AVG) avg_float4(avg, i, *reinterpret_cast<const f32x4*>(p + i * 4));
+      continue;
+    }
+    f32x4 pv = sgd_float4(p, g, buf, i, gs[r]);
+    if (AVG) {
+      asm volatile("" : "+v"(pv));
+      avg_float4(avg, i, pv);
+    }
+  }
+}
+
+using SgdGroupsKernel = decltype(&sgd_groups_kernel<false, false, false, false>);
+#define MMFN_SGD_ROW(MASK)                                                                                                      \
+  sgd_groups_kernel<false, false, false, MASK>, sgd_groups_kernel<true, false, false, MASK>,                                    \
+      sgd_groups_kernel<false, true, false, MASK>, sgd_groups_kernel<true, true, false, MASK>, nullptr,                         \
+      sgd_groups_kernel<true, false, true, MASK>, nullptr, sgd_groups_kernel<true, true, true, MASK>
+const SgdGroupsKernel kSgdGroups[16] = {MMFN_SGD_ROW(false), MMFN_SGD_ROW(true)};   // as kAdamwGroups
+#undef MMFN_SGD_ROW
+
+using SgdRowsKernel = decltype(&sgd_rows_kernel<false, false, false>);
+const SgdRowsKernel kSgdRows[8] = {   // as kAdamwRows
+    sgd_rows_kernel<false, false, false>, sgd_rows_kernel<true, false, false>, sgd_rows_kernel<false, true, false>,
+    sgd_rows_kernel<true, true, false>,   nullptr,                              sgd_rows_kernel<true, false, true>,
+    nullptr,                              sgd_rows_kernel<true, true, true>};
+}  // namespace
+
+extern "C" int mmfn_sgd_groups_f32(float* p, const float* g, float* buf, int64_t n, const uint8_t* group_of, const float* hyper,
+                                   int n_groups, const int64_t* step, int variant, const float* coef, float* avg,
+                                   const int64_t* n_averaged, const float* ema_w, int avg_mode, const int32_t* ok, void* stream) {
+  if (n <= 0) return 0;
+  if (variant < 0 || variant >= 16 || !kSgdGroups[variant]) return MMFN_EINVAL;
+  const bool with_coef = variant & MMFN_ADAMW_COEF, with_avg = variant & MMFN_ADAMW_AVG, guard = variant & MMFN_ADAMW_GUARD;
+  const bool mask = variant & MMFN_ADAMW_MASK;
+  const AvgArgs a = with_avg ? AvgArgs{avg, n_averaged, ema_w, avg_mode} : AvgArgs{};
+  if (!p || !g || !buf || ((uintptr_t)step & 7) || !adamw_args_ok(p, g, buf, buf, n, hyper, n_groups, step) ||
+      (with_coef && !coef) || (with_avg && !avg_args_ok(a)) || (guard && !flag_ok(ok)) || (mask && !group_of))
+    return MMFN_EINVAL;
+  hipLaunchKernelGGL(kSgdGroups[variant], dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, buf, n, group_of, hyper,
+                     n_groups, step, with_coef ? coef : nullptr, a, guard ? ok : nullptr);
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mmfn_sgd_rows_f32(float* p, const float* g, float* buf, int64_t n, const uint8_t* row_of, const float* hyper,
+                                 int n_groups, const int32_t* rows, int n_rows, const int64_t* class_steps, int n_classes, int variant,
+                                 const float* coef, float* avg, const int64_t* n_averaged, const float* ema_w, int avg_mode,
+                                 const int32_t* ok, void* stream) {
+  if (n <= 0) return 0;
+  if (variant < 0 || variant >= 8 || !kSgdRows[variant]) return MMFN_EINVAL;
+  const bool with_coef = variant & MMFN_ADAMW_COEF, with_avg = variant & MMFN_ADAMW_AVG, guard = variant & MMFN_ADAMW_GUARD;
+  const AvgArgs a = with_avg ? AvgArgs{avg, n_averaged, ema_w, avg_mode} : AvgArgs{};
+  if (!p || !g || !buf || !row_of || !rows || n_rows < 1 || n_rows > MMFN_ADAMW_MAX_ROWS || n_classes < 1 || n_classes > 65536 ||
+      ((uintptr_t)class_steps & 7) || !adamw_args_ok(p, g, buf, buf, n, hyper, n_groups, class_steps) || (with_coef && !coef) ||
+      (with_avg && !avg_args_ok(a)) || (guard && !flag_ok(ok)))
+    return MMFN_EINVAL;
+  AdamwRowMap map{};
+  for (int r = 0; r < n_rows; ++r) {   // rows: HOST memory, [n_rows][2] = (group, class), every entry inside its table
+    const int32_t grp = rows[2 * r], cls = rows[2 * r + 1];
+    if (grp < 0 || grp >= n_groups || cls < 0 || cls >= n_classes) return MMFN_EINVAL;
+    map.group[r] = (uint8_t)grp;
+    map.cls[r] = (uint16_t)cls;
+  }
+  hipLaunchKernelGGL(kSgdRows[variant], dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, buf, n, row_of, hyper, map,
+                     n_rows, class_steps, with_coef ? coef : nullptr, a, guard ? ok : nullptr);
   MMFN_LAUNCH_CHECK();
   return 0;
 }

@@ -1466,6 +1466,7 @@ class Engine(object):
         self._hyper_pinned, self._hyper_slot = None, 0
         self.opt_amsgrad = ()       # per optimizer group: amsgrad (set_amsgrad); the flags travel in the last column of opt_hyper
         self._hyper_flags = ()      # ... as set_hyper last wrote them: the AdamW launch follows the table
+        self.opt_kind = "adamw"     # the update rule of the optimizer launch (set_optimizer): "adamw" | "sgd"
         # gradient accumulation (accumulate_step) and global-norm clipping: allocated on first use only
         self.grad_acc = None        # fp32 [0, tail): the sum of the pending micro-steps' gradients
         self.accum_pending = 0      # micro-steps in grad_acc (host count: it picks the 1 / (k * world) of the final step)
@@ -2069,11 +2070,35 @@ class Engine(object):
             return
         if len(flags) > 16:
             raise ValueError("at most 16 optimizer groups")
+        if any(flags) and self.opt_kind != "adamw":
+            raise ValueError("amsgrad is a flag of AdamW groups: the engine's optimizer is %r (Engine.set_optimizer)" % self.opt_kind)
         if any(flags) and self.layout.max_exp_avg_sq is None:
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("max_exp_avg_sq must be allocated before a hipGraph capture: call Engine.set_amsgrad() before it")
             self.layout.ensure_max_exp_avg_sq()
         self.opt_amsgrad = flags
+
+    OPTIMIZERS = ("adamw", "sgd")
+
+    def set_optimizer(self, kind):
+        """The update rule of every optimizer step: "adamw" (the default; torch.optim.AdamW) or "sgd" (torch.optim.SGD with
+        momentum, optim.FusedSGD).  Everything around the launch is shared: the hyper table (an SGD row is (lr, momentum, dampening,
+        nesterov, weight_decay) in the place of AdamW's five), groups, frozen masks, step classes, clipping, the guard, the
+        average.  The momentum buffer is layout.exp_avg; the caller answers for what it holds when the kind changes
+        (optim.FusedSGD(reset_state=True)).  A captured step records the kind and refuses to replay after it changed
+        (parallel.GraphedStep).  amsgrad flags and "sgd" exclude each other."""
+        if kind not in self.OPTIMIZERS:
+            raise ValueError("optimizer kind must be one of %s, got %r" % (" / ".join(self.OPTIMIZERS), kind))
+        if kind == self.opt_kind:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("the optimizer kind changed inside a hipGraph capture")
+        if self.accum_pending:
+            raise RuntimeError("the optimizer kind changed while %d accumulated micro-step(s) are pending: finish them with "
+                               "train_step() or drop them with discard_accumulated() first" % self.accum_pending)
+        if kind != "adamw" and any(self.opt_amsgrad):
+            raise ValueError("amsgrad is on in an optimizer group: clear the flags (Engine.set_amsgrad) before switching to %r" % kind)
+        self.opt_kind = kind
 
     def amsgrad_flags(self, n_groups):
         """The amsgrad flags of a step with n_groups hyper rows (a group without a flag has none; a step with one row runs
@@ -2147,14 +2172,30 @@ class Engine(object):
         self.average = None
 
     def _adamw(self, n_groups, coef=None, ok=None):
-        """The AdamW launch over the trained range (coef: the clipping instance).  With an attached average it is folded into the
+        """The optimizer launch over the trained range - AdamW, or momentum SGD when set_optimizer("sgd") chose it - (coef: the
+        clipping instance).  With an attached average it is folded into the
         launch, then come the average's BatchNorm buffers and its count: three launches (+ a counter copy) instead of one.  ok:
         the non-finite guard's flag, every one of them behind it."""
         L, a = self.layout, self.average
         avg = None if a is None else (a.module._layout.params, a.n_averaged, a.ema_weight, a.mode_code)
         # amsgrad in some group of the table as set_hyper wrote it: the launch that also carries max_exp_avg_sq (None: the plain one)
         vmax = L.max_exp_avg_sq if any(self._hyper_flags[:n_groups]) else None
-        if not self.classes.uniform():
+        if self.opt_kind == "sgd":
+            # momentum SGD: the same three instances over (p, g, momentum buffer = exp_avg); a tensor's first step is the one
+            # its count reads 1 at, which the step classes make per tensor
+            if vmax is not None:
+                raise ValueError("amsgrad flags in the hyper table of an SGD step")
+            if not self.classes.uniform():
+                row_of, rows = self._rows(n_groups)
+                ops.sgd_rows(L.params, L.grads, L.exp_avg, self._class_steps, self.classes.n_classes, self.opt_hyper, n_groups,
+                             row_of, rows, n=L.tail, coef=coef, avg=avg, ok=ok)
+            elif self.frozen:
+                ops.sgd_groups(L.params, L.grads, L.exp_avg, self.step_count, self.opt_hyper, n_groups,
+                               group_of=self._group_table(n_groups), n=L.tail, coef=coef, avg=avg, ok=ok, mask=True)
+            else:
+                ops.sgd_groups(L.params, L.grads, L.exp_avg, self.step_count, self.opt_hyper, n_groups,
+                               group_of=self.opt_group_of if n_groups > 1 else None, n=L.tail, coef=coef, avg=avg, ok=ok)
+        elif not self.classes.uniform():
             # a tensor that steps has a count of its own: the instance whose bias corrections follow the step classes
             row_of, rows = self._rows(n_groups)
             ops.adamw_rows(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self._class_steps, self.classes.n_classes, self.opt_hyper,

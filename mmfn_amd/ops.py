@@ -1258,6 +1258,54 @@ def adamw_rows(p, g, m, v, class_steps, n_classes, hyper, n_groups, row_of, rows
           ptr(class_steps), n_classes, variant, ptr(coef), ptr(a), ptr(n_averaged), ptr(ema_weight), int(mode), ptr(ok), stream())
 
 
+def _check_momentum_buffer(buf, p, n):
+    if buf is None or buf.dtype != torch.float32 or buf.device != p.device or buf.numel() < n:
+        raise ValueError("buf (momentum_buffer) is a float32 tensor on the parameters' device with one entry per parameter of the range")
+
+
+def sgd_groups(p, g, buf, step, hyper, n_groups, group_of=None, n=None, coef=None, avg=None, ok=None, mask=False):
+    """torch.optim.SGD with the hyper-parameter rows (lr, momentum, dampening, nesterov, weight_decay, grad_scale) in device memory:
+    mmfn_sgd_groups_f32.  buf: the momentum buffer; *step == 1 makes this the first step (buf = d).  group_of / coef / avg / ok /
+    mask as in adamw_groups."""
+    n = p.numel() if n is None else n
+    _check_momentum_buffer(buf, p, n)
+    if mask and (group_of is None or group_of.dtype != torch.uint8 or group_of.numel() * 4 < n):
+        raise ValueError("the masked SGD launch needs a uint8 group table with one byte per float4 of the range")
+    a, n_averaged, ema_weight, mode = (None, None, None, 0) if avg is None else avg
+    if a is not None and a.numel() < n:
+        raise ValueError("average holds %d floats, the step covers %d" % (a.numel(), n))
+    if ok is not None and coef is None:
+        raise ValueError("the guarded SGD launch is the coefficient instance: pass coef")
+    variant = sum(bit for bit, arg in ((ADAMW_COEF, coef), (ADAMW_AVG, avg), (ADAMW_GUARD, ok)) if arg is not None)
+    if mask:
+        variant |= ADAMW_MASK
+    _call("mmfn_sgd_groups_f32", ptr(p), ptr(g), ptr(buf), n, ptr(group_of), ptr(hyper), n_groups, ptr(step), variant, ptr(coef),
+          ptr(a), ptr(n_averaged), ptr(ema_weight), int(mode), ptr(ok), stream())
+
+
+def sgd_rows(p, g, buf, class_steps, n_classes, hyper, n_groups, row_of, rows, n=None, coef=None, avg=None, ok=None):
+    """torch.optim.SGD with per-tensor step counts (mmfn_sgd_rows_f32): a row's class counter at 1 makes this the first step of
+    the row's tensors.  row_of / rows / class_steps as in adamw_rows; coef / avg / ok as in sgd_groups."""
+    n = p.numel() if n is None else n
+    _check_momentum_buffer(buf, p, n)
+    if row_of is None or row_of.dtype != torch.uint8 or row_of.numel() * 4 < n:
+        raise ValueError("the SGD launch with step classes needs a uint8 row table with one byte per float4 of the range")
+    if rows.device.type != "cpu" or rows.dtype != torch.int32 or rows.dim() != 2 or rows.shape[1] != 2 or not rows.is_contiguous():
+        raise ValueError("rows is a contiguous CPU int32 tensor [n_rows, 2] of (group, class)")
+    if not 1 <= rows.shape[0] <= ADAMW_MAX_ROWS:
+        raise ValueError("%d (group, step class) rows: the SGD launch holds at most %d" % (rows.shape[0], ADAMW_MAX_ROWS))
+    if class_steps.dtype != torch.int64 or class_steps.numel() < n_classes:
+        raise ValueError("class_steps holds %d %s counters, the launch reads %d int64" % (class_steps.numel(), class_steps.dtype, n_classes))
+    a, n_averaged, ema_weight, mode = (None, None, None, 0) if avg is None else avg
+    if a is not None and a.numel() < n:
+        raise ValueError("average holds %d floats, the step covers %d" % (a.numel(), n))
+    if ok is not None and coef is None:
+        raise ValueError("the guarded SGD launch is the coefficient instance: pass coef")
+    variant = sum(bit for bit, arg in ((ADAMW_COEF, coef), (ADAMW_AVG, avg), (ADAMW_GUARD, ok)) if arg is not None)
+    _call("mmfn_sgd_rows_f32", ptr(p), ptr(g), ptr(buf), n, ptr(row_of), ptr(hyper), n_groups, rows.data_ptr(), rows.shape[0],
+          ptr(class_steps), n_classes, variant, ptr(coef), ptr(a), ptr(n_averaged), ptr(ema_weight), int(mode), ptr(ok), stream())
+
+
 def class_steps_advance(class_steps, active, n_classes, ok=None):
     """class_steps[c] += 1 for every class c < n_classes whose byte in `active` (uint8, device) is set; ok: the guard's flag."""
     if class_steps.dtype != torch.int64 or active.dtype != torch.uint8 or min(class_steps.numel(), active.numel()) < n_classes:

@@ -290,6 +290,9 @@ class GraphedStep(object):
     Frozen parameters (Engine.trainable_mask): the capture holds the backward pruned for the requires_grad flags of that moment and
     the AdamW launch masked for them; a replay after the flags changed raises, like the checks below.
 
+    Optimizer kind (Engine.set_optimizer): the capture holds the AdamW or the momentum-SGD launch of that moment; a replay after
+    the kind changed raises.
+
     amsgrad (Engine.set_amsgrad): an optimizer step with amsgrad in some group is not captured yet - the capture is refused, and
     so is the replay of a step captured before amsgrad was switched on; such steps run eagerly (Engine.train_step).
 
@@ -317,6 +320,7 @@ class GraphedStep(object):
         self.lr, self.adam = lr, adam
         eng = engine
         self.guard = eng.nonfinite_guard   # the captured final_adam holds the guarded launches (or not): see __call__
+        self.kind = eng.opt_kind           # ... and the AdamW or the SGD launch (Engine.set_optimizer)
         self.mask = eng.trainable_mask()   # the pruned backward and the masked AdamW launch are captured for these flags
         if warm and variant != "step" and eng.accum_pending:
             raise RuntimeError("warm-up steps would consume the %d pending micro-steps: capture with warm=0" % eng.accum_pending)
@@ -426,6 +430,9 @@ class GraphedStep(object):
                                "state): capture the step again")
         if self.variant != "micro" and any(eng.opt_amsgrad):
             raise RuntimeError("amsgrad was switched on after this step was captured: amsgrad steps run eagerly (Engine.set_amsgrad)")
+        if self.variant != "micro" and eng.opt_kind != self.kind:
+            raise RuntimeError("this step was captured with the %s launch; the engine's optimizer is now %r: capture the step again"
+                               % (self.kind, eng.opt_kind))
         if self.variant != "micro" and eng.nonfinite_guard != self.guard:
             raise RuntimeError("this step was captured with the non-finite guard %s; the engine now has it %s: capture the step again"
                                % (("armed", "disarmed") if self.guard else ("disarmed", "armed")))

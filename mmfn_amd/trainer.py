@@ -220,6 +220,8 @@ class Trainer(object):
             sig = (StaticBatchStep.signature(inp, gt), variant, fold, clip is not None)
             if average is not None and final:   # a capture with the average in its AdamW launch is a shape of its own
                 sig = sig + ("average",)
+            if eng.opt_kind != "adamw" and final:   # (the optimizer launch of another update rule: Engine.set_optimizer)
+                sig = sig + (("optimizer", eng.opt_kind),)
             if eng.nonfinite_guard and final:   # (the guarded launches are a capture of their own; micro-steps have none)
                 sig = sig + ("guard",)
             if eng.frozen:   # (frozen parameters: the pruned backward and the masked AdamW are captures of their own, per set of flags)
@@ -457,17 +459,25 @@ def _hyper_rows(optimizer):
     return [(g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"]) for g in optimizer.param_groups]
 
 
+_SGD_KEYS = ("lr", "momentum", "dampening", "weight_decay", "nesterov")   # a torch.optim.SGD / FusedSGD group's hyper-parameters
+
+
 def sync_resume_state(trainer, optimizer, dist, src=0):
     """After rank `src` resumed from disk: every rank takes its epoch / iteration counters, loss history and the
-    optimizer hyper-parameters (lr, betas, eps, weight decay and the amsgrad flag per group).  Without this the ranks would iterate different
+    optimizer hyper-parameters (lr, betas, eps, weight decay and the amsgrad flag per group; an SGD optimizer's lr, momentum,
+    dampening, weight decay and nesterov instead).  Without this the ranks would iterate different
     epoch ranges (and deadlock in the gradient all-reduce when rank 0 leaves the loop first), seed their samplers
     differently and step with different learning rates.  Weights / moments / step counter travel separately
     (DataParallel.broadcast_parameters)."""
     payload = [None]
+    sgd = bool(optimizer.param_groups) and "momentum" in optimizer.param_groups[0]   # (chosen by what the groups hold)
     if dist.get_rank() == src:
-        payload[0] = {"table": trainer._log_table(),
-                      "groups": [dict({k: g[k] for k in ("lr", "betas", "eps", "weight_decay")}, amsgrad=bool(g.get("amsgrad", False)))
-                                 for g in optimizer.param_groups]}
+        if sgd:
+            groups = [{k: g[k] for k in _SGD_KEYS} for g in optimizer.param_groups]
+        else:
+            groups = [dict({k: g[k] for k in ("lr", "betas", "eps", "weight_decay")}, amsgrad=bool(g.get("amsgrad", False)))
+                      for g in optimizer.param_groups]
+        payload[0] = {"table": trainer._log_table(), "groups": groups}
     dist.broadcast_object_list(payload, src=src)
     st = payload[0]
     t = st["table"]
@@ -476,7 +486,12 @@ def sync_resume_state(trainer, optimizer, dist, src=0):
     trainer.train_loss, trainer.val_loss = list(t["train_loss"]), list(t["val_loss"])
     if len(st["groups"]) != len(optimizer.param_groups):
         raise ValueError("rank %d has %d optimizer groups, rank %d has %d" % (dist.get_rank(), len(optimizer.param_groups), src, len(st["groups"])))
+    if any(("momentum" in new) != sgd for new in st["groups"]):
+        raise ValueError("rank %d holds %s groups, rank %d sent the other optimizer's" % (dist.get_rank(), "SGD" if sgd else "AdamW", src))
     for g, new in zip(optimizer.param_groups, st["groups"]):
+        if sgd:   # (lr, momentum, dampening, weight_decay, nesterov)
+            g.update({k: new[k] for k in _SGD_KEYS})
+            continue
         g["lr"], g["betas"], g["eps"], g["weight_decay"] = new["lr"], tuple(new["betas"]), new["eps"], new["weight_decay"]
         g["amsgrad"] = new["amsgrad"]
     if hasattr(optimizer, "sync_amsgrad"):   # (FusedAdamW: the flags reach the engine, which allocates max_exp_avg_sq if need be)
