@@ -507,6 +507,35 @@ int mmfn_gru_head_fwd_f32(const float* z0, const float* target, const float* w_i
 int mmfn_gru_head_bwd_f32(const float* pred, const float* gt, const float* dpred, float gscale, const float* w_ih,
                           const float* w_hh, const float* w_out, const float* hs, const float* gates, const float* xin,
                           float* dz0, float* part, int B, int steps, void* stream);
+/* The two launches above with the objective as a parameter (Engine.set_loss, mmfn_amd.losses.WaypointLoss).  With e = pred - gt the
+ * per-element term rho(e) and its derivative are torch's:
+ *   MMFN_LOSS_L1         |e|                                              sign(e), sign(0) = 0
+ *   MMFN_LOSS_SMOOTH_L1  |e| < beta ? 0.5 e^2 / beta : |e| - 0.5 beta      |e| < beta ? e / beta : sign(e)      (beta = 0: L1)
+ *   MMFN_LOSS_HUBER      |e| <= delta ? 0.5 e^2 : delta (|e| - 0.5 delta)  |e| <= delta ? e : delta sign(e)
+ *   MMFN_LOSS_MSE        e^2                                              2 e
+ * loss_table: 16 floats in DEVICE memory, so a captured hipGraph stays valid when they change - [0] = beta or delta, [8 + t] = the
+ * horizon weight hw[t] of GRU step t (steps <= 8); `kind` is a launch argument.  sample_weight: [B] floats or NULL (= 1).
+ *   loss_terms[b] = sw[b] * sum_t hw[t] * sum_c rho(e[b,t,c]),   *loss = sum_b loss_terms[b] / (B * steps * 2)
+ * i.e. (sw[:,None,None] * hw[None,:,None] * rho(pred - gt)).mean(): no normalisation by the weights.  l1_terms (nullable): [B], the
+ * unweighted sum of |e| of the sample.  The backward forms dpred = sw[b] * hw[t] * rho'(e) * gscale and continues as
+ * mmfn_gru_head_bwd_f32 does.  With MMFN_LOSS_L1, hw = 1 and sw NULL or 1 every output carries the bits of the launches above.
+ * gt, loss_terms, loss_table are required; an unknown kind, steps > 8, B <= 0 or hs / gates / xin not all set or all NULL:
+ * MMFN_EINVAL, nothing is launched. */
+#define MMFN_LOSS_L1 0
+#define MMFN_LOSS_SMOOTH_L1 1
+#define MMFN_LOSS_HUBER 2
+#define MMFN_LOSS_MSE 3
+#define MMFN_LOSS_TABLE_FLOATS 16
+#define MMFN_LOSS_TABLE_HORIZON 8
+int mmfn_gru_head_fwd_loss_f32(const float* z0, const float* target, const float* w_ih, const float* w_hh, const float* b_ih,
+                               const float* b_hh, const float* w_out, const float* b_out, const float* gt, float* pred,
+                               float* hs, float* gates, float* xin, float* loss_terms, float* loss, int kind,
+                               const float* loss_table, const float* sample_weight, float* l1_terms, int B, int steps,
+                               void* stream);
+int mmfn_gru_head_bwd_loss_f32(const float* pred, const float* gt, float gscale, const float* w_ih, const float* w_hh,
+                               const float* w_out, const float* hs, const float* gates, const float* xin, float* dz0,
+                               float* part, int kind, const float* loss_table, const float* sample_weight, int B, int steps,
+                               void* stream);
 
 /* ---- optimizer (torch.optim.AdamW semantics, phase2_train_net.py:110,256) ---------------------- */
 int mmfn_step_advance(int64_t* step, void* stream);

@@ -1309,8 +1309,14 @@ class Head(object):
         self.grads = [layout.g("decoder.weight_ih"), layout.g("decoder.weight_hh"), layout.g("decoder.bias_ih"),
                       layout.g("decoder.bias_hh"), self.out.gw, self.out.gb]
         self.steps = pred_len
+        # the objective of the training forwards (Engine.set_loss): MMFN_LOSS_* and the 16 device floats the launches with the
+        # objective as a parameter read (None until a loss or a sample weight first needs them)
+        self.loss_kind = 0
+        self.loss_table = None
+        self.plain = True      # L1 without horizon weights: the original launches, unless the batch carries sample weights
+        self.lossy = False     # the last training forward with a loss ran the launches with the objective as a parameter
 
-    def fwd(self, ctx, fused, target, gt=None):
+    def fwd(self, ctx, fused, target, gt=None, sample_weight=None):
         bufs = ctx.bufs
         B = fused.shape[0]
         self.xs = [fused]
@@ -1328,21 +1334,36 @@ class Head(object):
         xin = bufs.get("head.xin", (B, S, 2)) if train else None
         lt = bufs.get("head.lt", (B,)) if gt is not None else None
         loss = bufs.get("head.loss", (1,)) if gt is not None else None
-        ops.gru_head_fwd(x, target, self.w_ih, self.w_hh, self.b_ih, self.b_hh, self.out.w, self.out.b, gt, pred, hs, gates, xin,
-                         lt, loss, S)
-        self.saved = (pred, gt, hs, gates, xin)
+        # the objective applies to training forwards only: an eval forward's loss stays the mean L1 (validation keeps its meaning)
+        lossy = train and gt is not None and (sample_weight is not None or not self.plain)
+        if lossy:
+            if self.loss_table is None:
+                raise RuntimeError("the loss table is not allocated (Engine.set_loss / Engine._loss_table)")
+            l1 = bufs.get("head.l1", (B,))
+            ops.gru_head_fwd_loss(x, target, self.w_ih, self.w_hh, self.b_ih, self.b_hh, self.out.w, self.out.b, gt, pred, hs, gates,
+                                  xin, lt, loss, self.loss_kind, self.loss_table, sample_weight, l1, S)
+        else:
+            ops.gru_head_fwd(x, target, self.w_ih, self.w_hh, self.b_ih, self.b_hh, self.out.w, self.out.b, gt, pred, hs, gates, xin,
+                             lt, loss, S)
+        if train and gt is not None:
+            self.lossy = lossy
+        self.saved = (pred, gt, hs, gates, xin, sample_weight if lossy else None, lossy)
         return pred, loss
 
     def bwd(self, ctx, dpred=None, gscale=None):
         bufs = ctx.bufs
-        pred, gt, hs, gates, xin = self.saved
+        pred, gt, hs, gates, xin, sample_weight, lossy = self.saved
         B, S = pred.shape[0], self.steps
         if gscale is None:
             gscale = 1.0 / (B * S * 2)
         npart = ops.lib().mmfn_gru_head_part_floats()
         part = bufs.get("head.part", (B, npart))
         dz = bufs.get("head.dz", (B, 64))
-        ops.gru_head_bwd(pred, gt, dpred, gscale, self.w_ih, self.w_hh, self.out.w, hs, gates, xin, dz, part, S)
+        if lossy and dpred is None:   # (an external gradient - the autograd entry - takes the original launch)
+            ops.gru_head_bwd_loss(pred, gt, gscale, self.w_ih, self.w_hh, self.out.w, hs, gates, xin, dz, part, self.loss_kind,
+                                  self.loss_table, sample_weight, S)
+        else:
+            ops.gru_head_bwd(pred, gt, dpred, gscale, self.w_ih, self.w_hh, self.out.w, hs, gates, xin, dz, part, S)
         tot = ops.colsum(part, bufs.get("head.partsum", (npart,)))
         o = 0
         for gbuf in self.grads:
@@ -1467,6 +1488,7 @@ class Engine(object):
         self.opt_amsgrad = ()       # per optimizer group: amsgrad (set_amsgrad); the flags travel in the last column of opt_hyper
         self._hyper_flags = ()      # ... as set_hyper last wrote them: the AdamW launch follows the table
         self.opt_kind = "adamw"     # the update rule of the optimizer launch (set_optimizer): "adamw" | "sgd"
+        self.loss = None            # the objective of the training forwards (set_loss): None = the reference's mean L1
         # gradient accumulation (accumulate_step) and global-norm clipping: allocated on first use only
         self.grad_acc = None        # fp32 [0, tail): the sum of the pending micro-steps' gradients
         self.accum_pending = 0      # micro-steps in grad_acc (host count: it picks the 1 / (k * world) of the final step)
@@ -1921,11 +1943,17 @@ class Engine(object):
         feats = [ops.upsample_add_fwd(f, tok, ctx.bufs.get("fuse3.%d" % m, f.shape, f.dtype), base[m], frames[m]) for m, f in enumerate(feats)]
         fused = ops.gap_sum_fwd(feats, ctx.bufs.get("fused", (B, 512)), frames=frames[:len(feats)])
         self.taps["fused"] = fused
-        pred, loss = self.head.fwd(ctx, fused, inp["target_point"], gt)
+        sw = inp.get("sample_weight") if training and gt is not None else None
+        if sw is not None:
+            if sw.dtype != torch.float32 or tuple(sw.shape) != (B,) or not sw.is_contiguous():
+                raise ValueError("inp['sample_weight'] must be a contiguous float32 tensor of shape [%d], got %s %s" % (
+                    B, sw.dtype, tuple(sw.shape)))
+            self._loss_table()
+        pred, loss = self.head.fwd(ctx, fused, inp["target_point"], gt, sw)
         return pred, loss
 
     def backward(self, dpred=None, gscale=None, on_stage=None, on_ready=None):
-        """Backward of the last training forward.  dpred None => gradient of the fused L1 loss.
+        """Backward of the last training forward.  dpred None => gradient of the forward's own loss (the mean L1, or what set_loss chose).
         on_stage(i) is called as soon as every gradient of backward stage i (params.FlatLayout.stage_of)
         has been written, so a data-parallel wrapper can start reducing that bucket.
         on_ready((stage, group)) is the finer hook: called - ON THE STREAM THAT WROTE THEM, which inside the branch lanes is a
@@ -2099,6 +2127,72 @@ class Engine(object):
         if kind != "adamw" and any(self.opt_amsgrad):
             raise ValueError("amsgrad is on in an optimizer group: clear the flags (Engine.set_amsgrad) before switching to %r" % kind)
         self.opt_kind = kind
+
+    # ------------------------------------------------------------------ objective (mmfn_amd.losses)
+    def set_loss(self, loss):
+        """The objective of every TRAINING forward with a ground truth (train_step, accumulate_step, their captured forms, forward(inp,
+        True, gt)): a losses.WaypointLoss, or None for the reference's mean L1.  An eval forward's loss stays the mean L1, so
+        validation losses keep their meaning across runs.  A batch may also carry inp["sample_weight"] ([B] float32 on the device), with
+        or without a loss object.  With a plain loss (None, or L1 without step weights) and no sample weights the head runs its
+        original two launches, bit for bit; anything else runs mmfn_gru_head_fwd_loss_f32 / mmfn_gru_head_bwd_loss_f32.  beta / delta
+        and the horizon weights live in a 16-float device table, written here, outside any capture: a captured step stays valid when
+        they change.  The kind is a launch argument: a captured step records it and refuses to replay after it changed
+        (parallel.GraphedStep).  Everything behind the head (accumulation, clipping, the guard, averaging, frozen parameters, the
+        optimizer launch, data parallel: each rank the mean over its own batch, as DDP) sees only the gradient."""
+        from .losses import WaypointLoss
+        if loss is not None and not isinstance(loss, WaypointLoss):
+            raise TypeError("set_loss takes a mmfn_amd.losses.WaypointLoss or None, got %r" % (loss,))
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("the loss changed inside a hipGraph capture")
+        if self.accum_pending:
+            raise RuntimeError("the loss changed while %d accumulated micro-step(s) are pending: finish them with "
+                               "train_step() or drop them with discard_accumulated() first" % self.accum_pending)
+        self._install_loss(loss)
+
+    def _install_loss(self, loss):
+        """set_loss behind its checks (Trainer.train restores the previous loss through it, also after an epoch that failed)."""
+        if loss is not None:
+            loss.check_steps(self.head.steps)
+        self.loss = loss
+        self.head.plain = loss is None or loss.is_plain()
+        self.head.loss_kind = 0 if loss is None else loss.kind_code
+        if self.head.loss_table is not None or not self.head.plain:
+            self._loss_table(write=True)
+
+    def _loss_table(self, write=False):
+        """The device table of the head's loss launches: allocated on first need (a loss that is not plain, a batch with sample
+        weights), never inside a capture; rewritten by every set_loss from then on."""
+        head = self.head
+        if head.loss_table is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the loss table must be allocated before a hipGraph capture: run one eager step of the batch "
+                                   "(or Engine.set_loss) before it")
+            head.loss_table = torch.zeros(16, dtype=torch.float32, device=self.device)
+            write = True
+        if write:
+            from .losses import PLAIN
+            head.loss_table.copy_(torch.tensor((self.loss or PLAIN).table(head.steps), dtype=torch.float32))
+        return head.loss_table
+
+    def loss_key(self):
+        """What a capture records of the objective: None for a plain loss, else its kind (beta / delta / horizon weights are device
+        memory and not part of a capture)."""
+        return None if self.head.plain else self.loss.kind
+
+    def sample_losses(self, batch=None):
+        """Device tensor [B]: each sample's share of the last forward's loss, sw[b] * sum_t hw[t] * sum_c rho(e) / (pred_len * 2) (their
+        mean is the loss).  No host sync; a view of a buffer the next forward of this batch size overwrites.  batch: the batch
+        size (default: the last forward's)."""
+        B = self._last[1] if batch is None else int(batch)
+        return self._bufs_for(B).get("head.lt", (B,)) / float(self.head.steps * 2)
+
+    def sample_l1(self, batch=None):
+        """As sample_losses, the unweighted mean |pred - gt| of each sample - comparable with the L1 validation loss whatever the
+        objective.  None when the last training forward ran the plain path (its sample_losses are these numbers)."""
+        if not self.head.lossy:
+            return None
+        B = self._last[1] if batch is None else int(batch)
+        return self._bufs_for(B).get("head.l1", (B,)) / float(self.head.steps * 2)
 
     def amsgrad_flags(self, n_groups):
         """The amsgrad flags of a step with n_groups hyper rows (a group without a flag has none; a step with one row runs

@@ -198,6 +198,11 @@ class MMFN(nn.Module):
         else:
             eng.attach_average(average)
 
+    def set_loss(self, loss):
+        """The objective of the fused training step: a mmfn_amd.losses.WaypointLoss (L1 / smooth-L1 / Huber / MSE, horizon weights), or
+        None for the reference's mean L1 (engine.Engine.set_loss).  Validation stays mean L1."""
+        self._engine_for().set_loss(loss)
+
     def guard_nonfinite(self, on=True):
         """Skip, on the device, every optimizer step of the fused path whose gradient norm is not finite: weights, moments,
         BatchNorm statistics and an attached average stay as they were (engine.Engine.set_nonfinite_guard); False disarms."""

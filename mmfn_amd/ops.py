@@ -1152,6 +1152,22 @@ def gru_head_bwd(pred, gt, dpred, gscale, w_ih, w_hh, w_out, hs, gates, xin, dz0
           ptr(gates), ptr(xin), ptr(dz0), ptr(part), B, steps, stream())
 
 
+def gru_head_fwd_loss(z0, target, w_ih, w_hh, b_ih, b_hh, w_out, b_out, gt, pred, hs, gates, xin, loss_terms, loss, kind, loss_table,
+                      sample_weight, l1_terms, steps):
+    """gru_head_fwd with the objective as a parameter (losses.WaypointLoss): kind = MMFN_LOSS_*, loss_table = 16 device floats
+    (beta / delta, horizon weights), sample_weight [B] or None, l1_terms [B] or None."""
+    B = z0.shape[0]
+    _call("mmfn_gru_head_fwd_loss_f32", ptr(z0), ptr(target), ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh), ptr(w_out), ptr(b_out),
+          ptr(gt), ptr(pred), ptr(hs), ptr(gates), ptr(xin), ptr(loss_terms), ptr(loss), int(kind), ptr(loss_table),
+          ptr(sample_weight), ptr(l1_terms), B, steps, stream())
+
+
+def gru_head_bwd_loss(pred, gt, gscale, w_ih, w_hh, w_out, hs, gates, xin, dz0, part, kind, loss_table, sample_weight, steps):
+    B = dz0.shape[0]
+    _call("mmfn_gru_head_bwd_loss_f32", ptr(pred), ptr(gt), float(gscale), ptr(w_ih), ptr(w_hh), ptr(w_out), ptr(hs), ptr(gates),
+          ptr(xin), ptr(dz0), ptr(part), int(kind), ptr(loss_table), ptr(sample_weight), B, steps, stream())
+
+
 def step_advance(step, ok=None):
     """step += 1; ok: the non-finite guard's device flag (int32), only when it is set."""
     if ok is not None:

@@ -293,6 +293,11 @@ class GraphedStep(object):
     Optimizer kind (Engine.set_optimizer): the capture holds the AdamW or the momentum-SGD launch of that moment; a replay after
     the kind changed raises.
 
+    Objective (Engine.set_loss): the capture holds the head launches of the loss kind of that moment (the original pair for a plain
+    loss, the pair with the objective as a parameter otherwise); a replay after the kind changed raises.  beta / delta and the horizon
+    weights are device memory: set_loss with a loss of the same kind rewrites the table and the capture stays valid.  Sample weights
+    are an input like any other (inp["sample_weight"]).
+
     amsgrad (Engine.set_amsgrad): an optimizer step with amsgrad in some group is not captured yet - the capture is refused, and
     so is the replay of a step captured before amsgrad was switched on; such steps run eagerly (Engine.train_step).
 
@@ -321,6 +326,7 @@ class GraphedStep(object):
         eng = engine
         self.guard = eng.nonfinite_guard   # the captured final_adam holds the guarded launches (or not): see __call__
         self.kind = eng.opt_kind           # ... and the AdamW or the SGD launch (Engine.set_optimizer)
+        self.loss_key = eng.loss_key()     # ... and the head launches of this objective (Engine.set_loss): every variant holds them
         self.mask = eng.trainable_mask()   # the pruned backward and the masked AdamW launch are captured for these flags
         if warm and variant != "step" and eng.accum_pending:
             raise RuntimeError("warm-up steps would consume the %d pending micro-steps: capture with warm=0" % eng.accum_pending)
@@ -338,6 +344,8 @@ class GraphedStep(object):
             eng._accum_buffer()
         if clip:
             eng._norm_state()
+        if inp.get("sample_weight") is not None:
+            eng._loss_table()   # (sample weights under a plain loss: the table of the loss launches, allocated outside the capture)
         self.n_groups = None
         if variant != "micro":
             self._write_rows()   # (the capture must find them set: Engine.set_hyper refuses to change the table inside one)
@@ -433,6 +441,9 @@ class GraphedStep(object):
         if self.variant != "micro" and eng.opt_kind != self.kind:
             raise RuntimeError("this step was captured with the %s launch; the engine's optimizer is now %r: capture the step again"
                                % (self.kind, eng.opt_kind))
+        if eng.loss_key() != self.loss_key:
+            raise RuntimeError("this step was captured with the %s loss; the engine's loss is now %r: capture the step again"
+                               % (self.loss_key or "plain L1", eng.loss_key() or "plain L1"))
         if self.variant != "micro" and eng.nonfinite_guard != self.guard:
             raise RuntimeError("this step was captured with the non-finite guard %s; the engine now has it %s: capture the step again"
                                % (("armed", "disarmed") if self.guard else ("disarmed", "armed")))

@@ -63,7 +63,7 @@ class Trainer(object):
 
     # ------------------------------------------------------------------ one epoch of training
     def train(self, model, dataloader_train, config, optimizer, dp=None, fused=True, log_every=50, on_log=None, graph=True,
-              lane_bucket=16, accum_steps=1, clip_grad_norm=None, average=None, skip_nonfinite=False):
+              lane_bucket=16, accum_steps=1, clip_grad_norm=None, average=None, skip_nonfinite=False, loss=None, sample_weight=None):
         """One epoch.  graph=True (fused path): the second batch of a given shape captures the step into hipGraphs over
         static input buffers and every later batch of that shape only copies its inputs and replays (the first one runs
         eagerly and sizes the buffers); lane sets are zero-padded to a multiple of `lane_bucket` lanes so that ragged
@@ -87,29 +87,41 @@ class Trainer(object):
         whose gradient norm is not finite is skipped on the device - weights, moments, BatchNorm statistics and the average stay
         as they were, the whole accumulation group is dropped.  on_log and recent.log gain "skipped_steps" (the run's count), the
         epoch's train_loss is the mean over the batches with a finite loss, and a log window (log_every batches, or the rest of
-        the epoch) in which EVERY optimizer step was skipped raises RuntimeError naming tensors with non-finite gradients."""
+        the epoch) in which EVERY optimizer step was skipped raises RuntimeError naming tensors with non-finite gradients.
+
+        loss (losses.WaypointLoss): the objective of the epoch's training steps - set on the engine for the epoch (Engine.set_loss)
+        and the previous one restored afterwards; None leaves the engine's loss as it is.  fused=False calls loss.reference in the
+        place of the L1 loss.  sample_weight: a callable (inp, gt) -> [B] float32 device tensor, evaluated per batch outside any
+        capture; its result travels as inp["sample_weight"] (weights from gt's lateral extent, from inp["velocity"], ...).
+        train_loss and on_log's "loss" are the objective; when it is not the plain mean L1, on_log also gets "l1", the window's mean
+        of the batches' unweighted L1 (summed on the device, read with the loss).  validate() stays mean L1."""
         if skip_nonfinite and not fused:
             raise NotImplementedError("skip_nonfinite is an option of the fused step (fused=True)")
-        if (average is None and not skip_nonfinite) or not fused:
+        if (average is None and not skip_nonfinite and loss is None) or not fused:
             return self._train(model, dataloader_train, config, optimizer, dp, fused, log_every, on_log, graph, lane_bucket,
-                               accum_steps, clip_grad_norm, average)
+                               accum_steps, clip_grad_norm, average, False, loss, sample_weight)
         eng = model._engine_for()
         if average is not None:
             eng.attach_average(average)
+        previous = eng.loss
         try:
+            if loss is not None:
+                eng.set_loss(loss)
             if skip_nonfinite:
                 eng.set_nonfinite_guard(True)
             return self._train(model, dataloader_train, config, optimizer, dp, fused, log_every, on_log, graph, lane_bucket,
-                               accum_steps, clip_grad_norm, average, skip_nonfinite)
+                               accum_steps, clip_grad_norm, average, skip_nonfinite, loss, sample_weight)
         finally:
             if skip_nonfinite:
                 eng.set_nonfinite_guard(False)
+            if loss is not None:
+                eng._install_loss(previous)
             if average is not None:
                 eng.detach_average()
 
     def _train(self, model, dataloader_train, config, optimizer, dp, fused, log_every, on_log, graph, lane_bucket, accum_steps,
-               clip_grad_norm, average, guard=False):
-        """Trainer.train's epoch loop (an attached average and the armed guard are the caller's)."""
+               clip_grad_norm, average, guard=False, loss_fn=None, sample_weight=None):
+        """Trainer.train's epoch loop (an attached average, the armed guard and the engine's loss are the caller's)."""
         accum_steps = int(accum_steps)
         if accum_steps < 1:
             raise ValueError("accum_steps must be >= 1, got %d" % accum_steps)
@@ -126,6 +138,11 @@ class Trainer(object):
         total = torch.zeros(1, dtype=torch.float32, device=model._layout.device)
         window = torch.zeros_like(total)
         num_batches = 0
+        if loss_fn is None:
+            loss_fn = eng.loss   # (a loss set on the engine outside this epoch: the autograd path follows it too)
+        # the objective is not the plain mean L1: the batches' unweighted L1 is summed beside it for on_log's "l1"
+        weighted = sample_weight is not None or not (loss_fn is None or loss_fn.is_plain())
+        l1_window = torch.zeros_like(total) if weighted else None
         if guard:
             # losses are summed over the batches where they are finite, counted on the device: [epoch, window]
             finite = torch.zeros(2, dtype=torch.float32, device=model._layout.device)
@@ -143,6 +160,9 @@ class Trainer(object):
                 adam = dict(groups=_hyper_rows(optimizer))
                 lr = optimizer.param_groups[0]["lr"]
                 inp = _bucket_lanes(inp, lane_bucket)  # in both modes, so that eager and replayed steps are bit-identical
+                if sample_weight is not None:   # evaluated here, outside the capture; an input of the step like any other
+                    inp = dict(inp)
+                    inp["sample_weight"] = sample_weight(inp, gt).to(torch.float32).contiguous()
                 in_group += 1
                 final = in_group == accum_steps or last   # (not accumulating: every batch is a group of its own, the plain step)
                 loss = self._step_call(eng, dp, inp, gt, lr, adam, final, accum_steps > 1, clip_grad_norm, graph, average)
@@ -150,13 +170,22 @@ class Trainer(object):
                     in_group = 0
                     if guard:
                         window_steps += 1
+                l1 = eng.sample_l1(gt.shape[0]) if weighted else None
+                if l1 is not None:
+                    l1 = l1.mean().view(1)
             else:
                 if dp is not None or isinstance(args, dict):
                     raise NotImplementedError("the autograd path takes reference-format batches on one GPU; use fused=True")
                 for p in model.parameters():
                     p.grad = None
                 pred = model(*args)
-                loss = torch.nn.functional.l1_loss(pred, gt, reduction="none").mean()
+                if weighted:
+                    from .losses import PLAIN
+                    sw = None if sample_weight is None else sample_weight(model._pack(*args), gt)
+                    loss = (loss_fn or PLAIN).reference(pred, gt, sw)
+                    l1 = torch.nn.functional.l1_loss(pred.detach(), gt).view(1)
+                else:
+                    loss = torch.nn.functional.l1_loss(pred, gt, reduction="none").mean()
                 loss.backward()
                 optimizer.step()
                 if average is not None:
@@ -166,8 +195,12 @@ class Trainer(object):
                 good = torch.isfinite(loss)
                 loss = torch.where(good, loss, torch.zeros_like(loss))
                 finite += good.to(finite.dtype)
+                if weighted and l1 is not None:
+                    l1 = torch.where(good, l1, torch.zeros_like(l1))
             total += loss
             window += loss
+            if weighted and l1 is not None:
+                l1_window += l1
             self.cur_iter += 1
             num_batches += 1
             if guard and num_batches % log_every == 0:
@@ -176,12 +209,18 @@ class Trainer(object):
                 self._check_progress(eng, window_steps, self.skipped_steps - window_skipped0)
                 window_steps, window_skipped0 = 0, self.skipped_steps
             if on_log is not None and num_batches % log_every == 0:
+                # (the objective and, beside it, the unweighted L1: one read of both)
+                sums = (torch.cat((window, l1_window)) if weighted else window).tolist()
                 if guard:   # (the window's mean over its finite losses)
-                    rec = {"loss": float(window.item()) / max(float(finite[1].item()), 1.0), "iter": self.cur_iter,
-                           "skipped_steps": self.skipped_steps}
+                    count = max(float(finite[1].item()), 1.0)
+                    rec = {"loss": sums[0] / count, "iter": self.cur_iter, "skipped_steps": self.skipped_steps}
                     finite[1] = 0
                 else:
-                    rec = {"loss": float(window.item()) / log_every, "iter": self.cur_iter}
+                    count = log_every
+                    rec = {"loss": sums[0] / count, "iter": self.cur_iter}
+                if weighted:
+                    rec["l1"] = sums[1] / count
+                    l1_window.zero_()
                 if clip_grad_norm is not None:   # (None until the first optimizer step of the run)
                     rec["grad_norm"] = None if eng.last_grad_norm is None else float(eng.last_grad_norm.item())
                 on_log(rec)
@@ -224,6 +263,8 @@ class Trainer(object):
                 sig = sig + (("optimizer", eng.opt_kind),)
             if eng.nonfinite_guard and final:   # (the guarded launches are a capture of their own; micro-steps have none)
                 sig = sig + ("guard",)
+            if eng.loss_key() is not None:   # (the head launches of another objective: Engine.set_loss; every variant holds them)
+                sig = sig + (("loss", eng.loss_key()),)
             if eng.frozen:   # (frozen parameters: the pruned backward and the masked AdamW are captures of their own, per set of flags)
                 sig = sig + (mask,)
             if eng.classes.epoch and final:   # (per-tensor step counts: the AdamW launch follows the step classes of the moment)
@@ -504,7 +545,7 @@ def _plain_state_dict(model):
 
 def fit(model, optimizer, train_loader, val_loader, config, logdir, epochs, val_every=1, save_every=1, dp=None, rank=0,
         on_log=None, dist=None, accum_steps=1, clip_grad_norm=None, average=None, average_every="step", average_start_epoch=0,
-        skip_nonfinite=False, unfreeze_at=None):
+        skip_nonfinite=False, unfreeze_at=None, loss=None, sample_weight=None):
     """The epoch loop of phase2_train_net.py:307-322: train every epoch; rank 0 validates every `val_every`
     epochs and saves every `save_every`.  Data parallel: pass `dp` (a parallel.DataParallel), or just the initialised
     torch.distributed module as `dist` - the transport is then chosen by parallel.connect: the C-ABI RCCL communicator when it
@@ -522,7 +563,8 @@ def fit(model, optimizer, train_loader, val_loader, config, logdir, epochs, val_
     start of that epoch every rank calls model.unfreeze(*prefixes) (a prefix that matches nothing raises, here, before the first
     step), and a resumed run applies the entries of the epochs up to the one it resumes into before its first step.  The tensors
     unfrozen late start their AdamW bias correction at step 1, as torch.optim.AdamW's per-parameter counts do (Engine.tensor_steps),
-    and the optimizer checkpoint carries those counts."""
+    and the optimizer checkpoint carries those counts.
+    loss / sample_weight: Trainer.train's options, every epoch (the objective of the training steps; validation stays mean L1)."""
     if average_every not in ("step", "epoch"):
         raise ValueError("average_every must be 'step' or 'epoch', got %r" % (average_every,))
     if dp is None and dist is not None and dist.get_world_size() > 1:
@@ -557,7 +599,7 @@ def fit(model, optimizer, train_loader, val_loader, config, logdir, epochs, val_
         averaging = average is not None and epoch >= average_start_epoch
         trainer.train(model, train_loader, config, optimizer, dp=dp, on_log=on_log if rank == 0 else None, accum_steps=accum_steps,
                       clip_grad_norm=clip_grad_norm, average=average if averaging and average_every == "step" else None,
-                      skip_nonfinite=skip_nonfinite)
+                      skip_nonfinite=skip_nonfinite, loss=loss, sample_weight=sample_weight)
         if averaging and average_every == "epoch":
             average.update_parameters(model)
         if epoch % val_every == 0 and rank == 0 and val_loader is not None:
