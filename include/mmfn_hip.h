@@ -567,7 +567,9 @@ int mmfn_weight_average_f32(float* avg, const float* src, int64_t n, const int64
  *   MASK   frozen parameters (requires_grad = False): a float4 whose group_of byte is MMFN_ADAMW_FROZEN neither loads nor stores
  *          p / m / v - no step, no weight decay, as torch skips a parameter without a gradient; with AVG it loads p alone and
  *          the average is still updated from it.  group_of is mandatory, also with one group.  Every other float4 gets the bits
- *          of the instance without MASK */
+ *          of the instance without MASK
+ * A NULL p / g / m / v / hyper / step, a p / g / m / v not 16-byte aligned or a step not 8-byte aligned is MMFN_EINVAL, as for
+ * every entry point of this family. */
 #define MMFN_ADAMW_COEF 1
 #define MMFN_ADAMW_AVG 2
 #define MMFN_ADAMW_GUARD 4
@@ -586,7 +588,7 @@ int mmfn_adamw_groups_f32(float* p, const float* g, float* m, float* v, int64_t 
  * hyper[group] and class_steps[class] exactly as mmfn_adamw_groups_f32 forms a group's from *step: a float4 of row (g, c) gets the
  * bits that entry point gives it with step = class_steps[c].  Byte MMFN_ADAMW_FROZEN keeps its meaning (MASK is implied; any byte
  * >= n_rows is treated alike).  variant: COEF / AVG / GUARD as above, without the MASK bit.  Any NULL or misaligned pointer the
- * launch would read, or a count out of range: MMFN_EINVAL. */
+ * launch would read, or a count out of range: MMFN_EINVAL, by the checks mmfn_adamw_groups_f32 and every entry point below share. */
 #define MMFN_ADAMW_MAX_ROWS 254
 int mmfn_adamw_rows_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* row_of, const float* hyper,
                         int n_groups, const int32_t* rows, int n_rows, const int64_t* class_steps, int n_classes, int variant,

@@ -2,9 +2,9 @@
 // torch.optim.AdamW defaults lr 1e-4, betas (0.9, 0.999), eps 1e-8, weight_decay 1e-2).
 // HBM-bound: 28 B/param (read p,g,m,v; write p,m,v) in one pass with 16-byte accesses.
 // The step count lives in device memory so the launch is hipGraph-replayable.  Per-tensor step counts (a tensor unfrozen late
-// starts its bias correction at 1, as torch.optim.AdamW's state[p]["step"]): one counter per step class, adamw_rows_kernel below.
-// Momentum SGD (torch.optim.SGD) is a second update rule on the same buffers, tables and counters: sgd_groups_kernel /
-// sgd_rows_kernel, 20 B/param with the momentum buffer in the place of the first moment.
+// starts its bias correction at 1, as torch.optim.AdamW's state[p]["step"]): one counter per step class, RowSlots below.
+// Momentum SGD (torch.optim.SGD) is a second update rule on the same buffers, tables and counters: SgdRule below, 20 B/param
+// with the momentum buffer in the place of the first moment.
 #include <algorithm>
 
 #include "common.h"
@@ -80,16 +80,18 @@ extern "C" int mmfn_adamw_f32(float* p, const float* g, float* m, float* v, int6
   return 0;
 }
 
-// ---- grouped AdamW: hyper-parameters in DEVICE memory -------------------------------------------------------------
+// ---- the grouped optimizer step: ONE kernel over update rules and slot maps, hyper-parameters in DEVICE memory -----------------
 // torch.optim.AdamW param_groups (the reference defines decay / no-decay groups, model_vec.py:179-209) + a learning rate
-// that may change every step without re-capturing a hipGraph: each group's (lr, beta1, beta2, eps, weight_decay,
-// grad_scale) is a row of `hyper` [n_groups][8] in HBM, read by the kernel; `group_of` holds one group id per FOUR
-// consecutive parameters (every tensor of the flat layout starts 16-byte aligned, so a float4 never straddles tensors);
-// NULL = everything in group 0.
+// that may change every step without re-capturing a hipGraph: each group's hyper-parameters are a row of `hyper` [n_groups][8]
+// in HBM, read by the kernel.  One byte per FOUR consecutive parameters (every tensor of the flat layout starts 16-byte aligned,
+// so a float4 never straddles tensors) names the float4's SLOT: the scalars it steps with, formed once per block into LDS.
+//   slot map  GroupSlots: slot = hyper group, one step count *step for all.  RowSlots: slot = ROW = (hyper group, step class).
+//   rule      AdamwRule (28 B/param), AdamwAmsRule (+ max_exp_avg_sq, 36 B/param of an amsgrad group), SgdRule (20 B/param).
+// A rule provides Scalars (32 B, one per slot), State (its state streams, passed by value; ok(): the host's pointer check),
+// scalars<COEF>(hyper row, step count, coef) and step4(p, g, state, i, scalars), which steps one float4 and returns the new
+// parameter; kClampSlot says what a stray group byte does.  A new rule is such a struct plus its two extern "C" entry points.
 #define MMFN_ADAMW_MAX_GROUPS 16
 namespace {
-struct GroupScalars { float step_size, decay, bc2_sqrt, beta1, beta2, eps, grad_scale, pad; };
-
 // ---- weight averaging (torch.optim.swa_utils.AveragedModel) --------------------------------------------------------------
 // avg = src at the first update (*n_averaged == 0), else ATen's lerp(avg, src, w).  w as torch forms it: EMA lerps with the
 // Python float 1 - decay rounded to fp32 (the host writes it to *ema_w), SWA with 1 / (n_averaged + 1), the reciprocal of an
@@ -117,50 +119,51 @@ __device__ inline f32x4 lerp4(f32x4 a, f32x4 p, float w) {
   return r;
 }
 
-// COEF: every group's grad_scale is multiplied by *coef (the clip_grad_norm_ coefficient, written on the device by
-// mmfn_grad_norm_finalize); COEF = false is the plain grouped step.  AVG: the new parameter is also folded into avg.avg
-// (the weight average), from registers: 8 B more per parameter instead of a 12 B pass of its own.  GUARD (with COEF only): *ok
-// is the non-finite guard's flag (mmfn_grad_norm_finalize_guard); when it is 0 the whole grid returns before it reads or writes
-// anything, so parameters, moments and the average keep their bits.  MASK: a float4 whose group_of byte is MMFN_ADAMW_FROZEN
-// belongs to a parameter that is not trained (requires_grad = False): torch skips such a parameter entirely, so the float4 neither
-// loads nor stores p / m / v (no weight decay either); with AVG it loads p alone and the average still follows it, as AveragedModel
-// lerps every parameter.  A template bit and not a branch of the other instances: they keep their code
-template <bool COEF, bool AVG, bool GUARD, bool MASK>
-__global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                           float* __restrict__ v, int64_t n, const uint8_t* __restrict__ group_of,
-                                                           const float* __restrict__ hyper, int n_groups,
-                                                           const int64_t* __restrict__ step, const float* __restrict__ coef,
-                                                           AvgArgs avg, const int32_t* __restrict__ ok) {
-  if (GUARD && !*ok) return;   // uniform over the grid: no barrier is left behind
-  __shared__ GroupScalars gs[MMFN_ADAMW_MAX_GROUPS];
-  if ((int)threadIdx.x < n_groups) {
-    const float* h = hyper + threadIdx.x * 8;
-    const double t = (double)*step;
-    const double lr = (double)h[0], beta1 = (double)h[1], beta2 = (double)h[2];
-    GroupScalars s;
-    s.step_size = (float)(lr / (1.0 - pow(beta1, t)));
-    s.decay = (float)(1.0 - lr * (double)h[4]);
-    s.bc2_sqrt = (float)sqrt(1.0 - pow(beta2, t));
-    s.beta1 = h[1]; s.beta2 = h[2]; s.eps = h[3]; s.grad_scale = COEF ? h[5] * *coef : h[5]; s.pad = 0.f;
-    gs[threadIdx.x] = s;
+// the average's update of one float4 from the parameter pf; the count and the weight are uniform loads: the first update copies
+// the parameter, later ones lerp
+__device__ inline void avg_float4(const AvgArgs& avg, int64_t i, f32x4 pf) {
+  f32x4 out = pf;
+  if (*avg.n_averaged != 0) out = lerp4(*reinterpret_cast<const f32x4*>(avg.avg + i * 4), pf, avg_weight(avg));
+  *reinterpret_cast<f32x4*>(avg.avg + i * 4) = out;
+}
+
+inline bool aligned16(const void* a, const void* b = nullptr) { return !(((uintptr_t)a | (uintptr_t)b) & 15); }
+
+// ---- AdamW: hyper row {lr, beta1, beta2, eps, weight_decay, grad_scale, 0, amsgrad} ----------------------------------------------
+struct GroupScalars { float step_size, decay, bc2_sqrt, beta1, beta2, eps, grad_scale, pad; };
+
+// scalar prep in fp64 like torch's Python-side arithmetic, then rounded once to fp32; pad carries the amsgrad flag
+template <bool COEF, bool AMS>
+__device__ inline GroupScalars adamw_scalars(const float* __restrict__ h, int64_t count, const float* __restrict__ coef) {
+  const double t = (double)count;
+  const double lr = (double)h[0], beta1 = (double)h[1], beta2 = (double)h[2];
+  GroupScalars s;
+  s.step_size = (float)(lr / (1.0 - pow(beta1, t)));
+  s.decay = (float)(1.0 - lr * (double)h[4]);
+  s.bc2_sqrt = (float)sqrt(1.0 - pow(beta2, t));
+  s.beta1 = h[1]; s.beta2 = h[2]; s.eps = h[3]; s.grad_scale = COEF ? h[5] * *coef : h[5]; s.pad = AMS ? h[7] : 0.f;
+  return s;
+}
+
+struct AdamwRule {
+  using Scalars = GroupScalars;
+  struct State {
+    float* __restrict__ m;
+    float* __restrict__ v;
+    bool ok() const { return m && v && aligned16(m, v); }
+  };
+  static constexpr bool kClampSlot = false;   // a stray group byte indexes the scalars unclamped (the callers' tables are checked)
+  template <bool COEF>
+  static __device__ inline Scalars scalars(const float* __restrict__ h, int64_t count, const float* __restrict__ coef) {
+    return adamw_scalars<COEF, false>(h, count, coef);
   }
-  __syncthreads();
-  const int64_t n4 = (n + 3) >> 2;   // the flat buffers are padded to a multiple of 4 floats
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-    if (MASK && group_of[i] == MMFN_ADAMW_FROZEN) {
-      if (AVG) {
-        const f32x4 pf = *reinterpret_cast<const f32x4*>(p + i * 4);
-        f32x4 out = pf;
-        if (*avg.n_averaged != 0) out = lerp4(*reinterpret_cast<const f32x4*>(avg.avg + i * 4), pf, avg_weight(avg));
-        *reinterpret_cast<f32x4*>(avg.avg + i * 4) = out;
-      }
-      continue;
-    }
-    const GroupScalars s = gs[group_of ? group_of[i] : 0];
+  // The arithmetic relies on the contractions the compiler chooses for it (AdamwAmsRule spells them out): no fp contract pragma
+  static __device__ inline f32x4 step4(float* __restrict__ p, const float* __restrict__ g, const State& st, int64_t i,
+                                       const Scalars& s) {
     f32x4 pv = *reinterpret_cast<f32x4*>(p + i * 4);
     f32x4 gv = *reinterpret_cast<const f32x4*>(g + i * 4);
-    f32x4 mv = *reinterpret_cast<f32x4*>(m + i * 4);
-    f32x4 vv = *reinterpret_cast<f32x4*>(v + i * 4);
+    f32x4 mv = *reinterpret_cast<f32x4*>(st.m + i * 4);
+    f32x4 vv = *reinterpret_cast<f32x4*>(st.v + i * 4);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float gg = gv[e] * s.grad_scale;
@@ -171,16 +174,215 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p
       pv[e] = pv[e] - s.step_size * (mv[e] / denom);
     }
     *reinterpret_cast<f32x4*>(p + i * 4) = pv;
-    *reinterpret_cast<f32x4*>(m + i * 4) = mv;
-    *reinterpret_cast<f32x4*>(v + i * 4) = vv;
-    if (AVG) {   // the count and the weight are uniform loads: the first update copies the new parameter, later ones lerp
-      // an empty asm makes the new parameter opaque here: without it the compiler packs and contracts the AdamW arithmetic
-      // above differently once the lerp also reads it, and the step stops being bit-identical to the plain instance
-      f32x4 out = pv;
-      asm volatile("" : "+v"(out));
-      pv = out;
-      if (*avg.n_averaged != 0) out = lerp4(*reinterpret_cast<const f32x4*>(avg.avg + i * 4), pv, avg_weight(avg));
-      *reinterpret_cast<f32x4*>(avg.avg + i * 4) = out;
+    *reinterpret_cast<f32x4*>(st.m + i * 4) = mv;
+    *reinterpret_cast<f32x4*>(st.v + i * 4) = vv;
+    return pv;
+  }
+};
+
+// ---- amsgrad (torch.optim.AdamW(amsgrad=True), the single-tensor non-capturable form) ------------------------------------------
+// A fifth stream vmax holds the running maximum of the second moment: vmax = maximum(vmax, v_new), and the denominator is built
+// from sqrtf(vmax) instead of sqrtf(v_new).  amsgrad is a per-group property: hyper[group][7] != 0 switches it on, and a float4 of
+// a group without it neither loads nor stores vmax and gets the bits of AdamwRule.
+// torch.maximum: NaN when either operand is NaN (fmaxf would drop it)
+__device__ inline float max_nan(float a, float b) { return (a == a && !(b <= a)) ? b : a; }
+
+struct AdamwAmsRule {
+  using Scalars = GroupScalars;
+  struct State {
+    float* __restrict__ m;
+    float* __restrict__ v;
+    float* __restrict__ vmax;
+    bool ok() const { return m && v && vmax && aligned16(m, v) && aligned16(vmax); }
+  };
+  static constexpr bool kClampSlot = false;   // as AdamwRule
+  template <bool COEF>
+  static __device__ inline Scalars scalars(const float* __restrict__ h, int64_t count, const float* __restrict__ coef) {
+    return adamw_scalars<COEF, true>(h, count, coef);
+  }
+  // The element arithmetic is written out operation by operation, with the contractions the compiler chose for AdamwRule as
+  // explicit fmaf calls and contraction switched off for the rest, so that the bits do not depend on what else reads the values
+  // here: g * grad_scale - m is one fma, so are the two moment updates and p * decay - step_size * q.
+  static __device__ inline f32x4 step4(float* __restrict__ p, const float* __restrict__ g, const State& st, int64_t i,
+                                       const Scalars& s) {
+#pragma clang fp contract(off)
+    const bool ams = s.pad != 0.f;
+    f32x4 pv = *reinterpret_cast<f32x4*>(p + i * 4);
+    const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i * 4);
+    f32x4 mv = *reinterpret_cast<f32x4*>(st.m + i * 4);
+    f32x4 vv = *reinterpret_cast<f32x4*>(st.v + i * 4);
+    f32x4 xv = vv;
+    if (ams) xv = *reinterpret_cast<f32x4*>(st.vmax + i * 4);
+    const float omb1 = 1.0f - s.beta1, omb2 = 1.0f - s.beta2;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float gg = gv[e] * s.grad_scale;
+      mv[e] = __builtin_fmaf(omb1, __builtin_fmaf(gv[e], s.grad_scale, -mv[e]), mv[e]);
+      vv[e] = __builtin_fmaf(s.beta2, vv[e], gg * (omb2 * gg));
+      xv[e] = ams ? max_nan(xv[e], vv[e]) : vv[e];
+      const float denom = sqrtf(xv[e]) / s.bc2_sqrt + s.eps;
+      pv[e] = __builtin_fmaf(s.decay, pv[e], -(s.step_size * (mv[e] / denom)));
+    }
+    *reinterpret_cast<f32x4*>(p + i * 4) = pv;
+    *reinterpret_cast<f32x4*>(st.m + i * 4) = mv;
+    *reinterpret_cast<f32x4*>(st.v + i * 4) = vv;
+    if (ams) *reinterpret_cast<f32x4*>(st.vmax + i * 4) = xv;
+    return pv;
+  }
+};
+
+// ---- momentum SGD (torch.optim.SGD, the single-tensor form) ----------------------------------------------------------------------
+// One state stream buf (torch's momentum_buffer): 20 B per parameter (read p, g, buf; write p, buf), 12 B for a float4 of a
+// group with momentum 0, which neither loads nor stores buf.  hyper row: {lr, momentum, dampening, nesterov, weight_decay,
+// grad_scale, max_norm, 0}.  Per element
+//     d   = g * grad_scale + weight_decay * p          (coupled decay)
+//     buf = first ? d : momentum * buf + (1 - dampening) * d
+//     p   = p - lr * (nesterov ? d + momentum * buf : buf)
+// first: the slot's step count after the advance is 1 (torch: momentum_buffer is None).
+struct SgdScalars { float lr, momentum, omd, wd, grad_scale, nesterov, first, pad; };
+
+struct SgdRule {
+  using Scalars = SgdScalars;
+  struct State {
+    float* __restrict__ buf;
+    bool ok() const { return buf && aligned16(buf); }
+  };
+  static constexpr bool kClampSlot = true;   // a group byte that names no group of the table reads group 0, never past the LDS
+  template <bool COEF>
+  static __device__ inline Scalars scalars(const float* __restrict__ h, int64_t t, const float* __restrict__ coef) {
+    SgdScalars s;
+    s.lr = h[0]; s.momentum = h[1];
+    s.omd = (float)(1.0 - (double)h[2]);   // in fp64 like torch's Python-side 1 - dampening, rounded once
+    s.wd = h[4]; s.grad_scale = COEF ? h[5] * *coef : h[5];
+    s.nesterov = h[3]; s.first = t == 1 ? 1.f : 0.f; s.pad = 0.f;
+    return s;
+  }
+  // Written operation by operation with explicit fmaf calls and contraction switched off for the rest (as AdamwAmsRule), so
+  // that the bits do not depend on the instance around it.
+  static __device__ inline f32x4 step4(float* __restrict__ p, const float* __restrict__ g, const State& st, int64_t i,
+                                       const Scalars& s) {
+#pragma clang fp contract(off)
+    const bool mom = s.momentum != 0.f, first = s.first != 0.f, nesterov = s.nesterov != 0.f, decay = s.wd != 0.f;
+    f32x4 pv = *reinterpret_cast<f32x4*>(p + i * 4);
+    const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i * 4);
+    f32x4 bv = {0.f, 0.f, 0.f, 0.f};
+    if (mom && !first) bv = *reinterpret_cast<f32x4*>(st.buf + i * 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float gg = gv[e] * s.grad_scale;
+      const float d = decay ? __builtin_fmaf(s.wd, pv[e], gg) : gg;
+      float u = d;
+      if (mom) {
+        bv[e] = first ? d : __builtin_fmaf(s.omd, d, s.momentum * bv[e]);
+        u = nesterov ? __builtin_fmaf(s.momentum, bv[e], d) : bv[e];
+      }
+      pv[e] = __builtin_fmaf(-s.lr, u, pv[e]);
+    }
+    *reinterpret_cast<f32x4*>(p + i * 4) = pv;
+    if (mom) *reinterpret_cast<f32x4*>(st.buf + i * 4) = bv;
+    return pv;
+  }
+};
+
+// ---- slot maps --------------------------------------------------------------------------------------------------------------------
+// what the entry points hand a slot map's make(): the checked host-side description of the groups, counters and rows
+struct SlotArgs {
+  int n_groups;
+  const int64_t* steps;   // *step, or class_steps [n_classes]: device memory, 8-byte aligned
+  const int32_t* rows;    // HOST memory, [n_rows][2] = (group, class)
+  int n_rows, n_classes;
+};
+inline bool groups_ok(const SlotArgs& a) {
+  return a.n_groups >= 1 && a.n_groups <= MMFN_ADAMW_MAX_GROUPS && a.steps && !((uintptr_t)a.steps & 7);
+}
+
+// slot = hyper group; NULL bytes = everything in group 0.  MASK: byte MMFN_ADAMW_FROZEN is a float4 of a parameter that is not
+// trained (requires_grad = False); the bytes are then mandatory, also with one group
+struct GroupSlots {
+  static constexpr int kMax = MMFN_ADAMW_MAX_GROUPS, kVariants = 16;
+  static constexpr bool kMaskImplied = false;
+  int n;
+  const int64_t* step;
+  __device__ int group(int s) const { return s; }
+  __device__ int64_t count(int) const { return *step; }
+  template <bool MASK, bool CLAMP>
+  __device__ int slot(const uint8_t* __restrict__ slot_of, int64_t i) const {
+    if (MASK && slot_of[i] == MMFN_ADAMW_FROZEN) return -1;
+    const int b = slot_of ? slot_of[i] : 0;
+    return (CLAMP && b >= n) ? 0 : b;
+  }
+  static bool make(GroupSlots& s, const SlotArgs& a, const uint8_t* slot_of, bool mask) {
+    s = GroupSlots{a.n_groups, a.steps};
+    return groups_ok(a) && (slot_of || !mask);
+  }
+};
+
+// Per-tensor step counts: torch.optim.AdamW keeps state[p]["step"] per parameter and advances it only on the steps where the
+// parameter has a gradient, so a tensor unfrozen late starts its bias correction at 1.  Tensors that took part in exactly the same
+// step launches form a step CLASS with one int64 counter in class_steps (device memory).  slot = ROW = (hyper group, step class):
+// the same bytes move as with GroupSlots, no per-tensor id stream.  The row map travels as a kernel argument, checked on the host.
+struct AdamwRowMap {
+  uint16_t cls[MMFN_ADAMW_MAX_ROWS];
+  uint8_t group[MMFN_ADAMW_MAX_ROWS];
+};
+struct RowSlots {
+  static constexpr int kMax = MMFN_ADAMW_MAX_ROWS, kVariants = 8;   // 254 * 32 B = 8128 B of LDS
+  static constexpr bool kMaskImplied = true;                        // only the MASK instances exist, under the variants without the bit
+  AdamwRowMap map;
+  int n;
+  const int64_t* class_steps;
+  __device__ int group(int s) const { return map.group[s]; }
+  __device__ int64_t count(int s) const { return class_steps[map.cls[s]]; }
+  template <bool MASK, bool CLAMP>
+  __device__ int slot(const uint8_t* __restrict__ slot_of, int64_t i) const {
+    const int r = slot_of[i];
+    return r >= n ? -1 : r;   // MMFN_ADAMW_FROZEN (a byte that names no row is treated alike: it never indexes past the rows in LDS)
+  }
+  static bool make(RowSlots& s, const SlotArgs& a, const uint8_t* slot_of, bool) {
+    if (!groups_ok(a) || !slot_of || !a.rows || a.n_rows < 1 || a.n_rows > MMFN_ADAMW_MAX_ROWS || a.n_classes < 1 || a.n_classes > 65536)
+      return false;
+    s.n = a.n_rows;
+    s.class_steps = a.steps;
+    for (int r = 0; r < a.n_rows; ++r) {   // every entry inside its table
+      const int32_t grp = a.rows[2 * r], cls = a.rows[2 * r + 1];
+      if (grp < 0 || grp >= a.n_groups || cls < 0 || cls >= a.n_classes) return false;
+      s.map.group[r] = (uint8_t)grp;
+      s.map.cls[r] = (uint16_t)cls;
+    }
+    return true;
+  }
+};
+
+// COEF: every slot's grad_scale is multiplied by *coef (the clip_grad_norm_ coefficient, written on the device by
+// mmfn_grad_norm_finalize); COEF = false is the plain grouped step.  AVG: the new parameter is also folded into avg.avg
+// (the weight average), from registers: 8 B more per parameter instead of a 12 B pass of its own.  GUARD (with COEF only): *ok
+// is the non-finite guard's flag (mmfn_grad_norm_finalize_guard); when it is 0 the whole grid returns before it reads or writes
+// anything, so parameters, state and the average keep their bits.  MASK: a frozen float4 (slot < 0) belongs to a parameter that
+// is not trained: torch skips such a parameter entirely, so the float4 neither loads nor stores p or the state (no weight decay
+// either); with AVG it loads p alone and the average still follows it, as AveragedModel lerps every parameter.
+template <class Rule, class Slots, bool COEF, bool AVG, bool GUARD, bool MASK>
+__global__ __launch_bounds__(256) void optim_step_kernel(float* __restrict__ p, const float* __restrict__ g, typename Rule::State st,
+                                                         int64_t n, const uint8_t* __restrict__ slot_of,
+                                                         const float* __restrict__ hyper, Slots slots, const float* __restrict__ coef,
+                                                         AvgArgs avg, const int32_t* __restrict__ ok) {
+  if (GUARD && !*ok) return;   // uniform over the grid: no barrier is left behind
+  __shared__ typename Rule::Scalars gs[Slots::kMax];
+  if ((int)threadIdx.x < slots.n)
+    gs[threadIdx.x] = Rule::template scalars<COEF>(hyper + slots.group(threadIdx.x) * 8, slots.count(threadIdx.x), coef);
+  __syncthreads();
+  const int64_t n4 = (n + 3) >> 2;   // the flat buffers are padded to a multiple of 4 floats
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    const int s = slots.template slot<MASK, Rule::kClampSlot>(slot_of, i);
+    if (s < 0) {
+      if (AVG) avg_float4(avg, i, *reinterpret_cast<const f32x4*>(p + i * 4));
+      continue;
+    }
+    f32x4 pv = Rule::step4(p, g, st, i, gs[s]);
+    if (AVG) {
+      // an empty asm makes the new parameter opaque here: without it the compiler packs and contracts the rule's arithmetic
+      // differently once the lerp also reads it, and the step stops being bit-identical to the instance without AVG
+      asm volatile("" : "+v"(pv));
+      avg_float4(avg, i, pv);
     }
   }
 }
@@ -198,132 +400,6 @@ __global__ __launch_bounds__(256) void weight_average_kernel(const float* __rest
   }
 }
 
-constexpr int kAdamwMaxBlocks = 4096;   // beyond 4 * 256 * this many floats the grid-stride loops go round again
-int adamw_blocks(int64_t n) { return (int)std::min<int64_t>(ceil_div64(n / 4, 256), kAdamwMaxBlocks); }
-
-bool adamw_args_ok(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, int n_groups, const int64_t* step) {
-  return step && hyper && n_groups >= 1 && n_groups <= MMFN_ADAMW_MAX_GROUPS && !(n & 3) &&
-         !(((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15);
-}
-
-// the average: 16-byte aligned floats, the count (and for EMA the weight) in device memory, a known mode
-bool avg_args_ok(const AvgArgs& a) {
-  if (a.mode != MMFN_AVG_EMA && a.mode != MMFN_AVG_SWA) return false;
-  if (!a.avg || ((uintptr_t)a.avg & 15) || !a.n_averaged || ((uintptr_t)a.n_averaged & 7)) return false;
-  return a.mode != MMFN_AVG_EMA || (a.ema_w && !((uintptr_t)a.ema_w & 3));
-}
-bool flag_ok(const int32_t* ok) { return ok && !((uintptr_t)ok & 3); }   // the non-finite guard's device flag
-}  // namespace
-
-// One entry point for the instances of adamw_groups_kernel: the bits of `variant` (MMFN_ADAMW_COEF | _AVG | _GUARD | _MASK) are the
-// template arguments.  A set bit makes its pointers mandatory; the pointers of a clear bit are ignored.
-namespace {
-using AdamwGroupsKernel = decltype(&adamw_groups_kernel<false, false, false, false>);
-#define MMFN_ADAMW_ROW(MASK)                                                                                                    \
-  adamw_groups_kernel<false, false, false, MASK>, adamw_groups_kernel<true, false, false, MASK>,                                \
-      adamw_groups_kernel<false, true, false, MASK>, adamw_groups_kernel<true, true, false, MASK>, nullptr,                     \
-      adamw_groups_kernel<true, false, true, MASK>, nullptr, adamw_groups_kernel<true, true, true, MASK>
-const AdamwGroupsKernel kAdamwGroups[16] = {   // by variant; nullptr: GUARD without COEF, which is not built
-    MMFN_ADAMW_ROW(false), MMFN_ADAMW_ROW(true)};
-#undef MMFN_ADAMW_ROW
-}  // namespace
-
-extern "C" int mmfn_adamw_groups_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of,
-                                     const float* hyper, int n_groups, const int64_t* step, int variant, const float* coef,
-                                     float* avg, const int64_t* n_averaged, const float* ema_w, int avg_mode, const int32_t* ok,
-                                     void* stream) {
-  if (n <= 0) return 0;
-  if (variant < 0 || variant >= 16 || !kAdamwGroups[variant]) return MMFN_EINVAL;
-  const bool with_coef = variant & MMFN_ADAMW_COEF, with_avg = variant & MMFN_ADAMW_AVG, guard = variant & MMFN_ADAMW_GUARD;
-  const bool mask = variant & MMFN_ADAMW_MASK;
-  const AvgArgs a = with_avg ? AvgArgs{avg, n_averaged, ema_w, avg_mode} : AvgArgs{};
-  if (!adamw_args_ok(p, g, m, v, n, hyper, n_groups, step) || (with_coef && !coef) || (with_avg && !avg_args_ok(a)) ||
-      (guard && !flag_ok(ok)) || (mask && !group_of))
-    return MMFN_EINVAL;
-  hipLaunchKernelGGL(kAdamwGroups[variant], dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, group_of, hyper,
-                     n_groups, step, with_coef ? coef : nullptr, a, guard ? ok : nullptr);
-  MMFN_LAUNCH_CHECK();
-  return 0;
-}
-
-// ---- grouped AdamW with per-tensor step counts ----------------------------------------------------------------------------------
-// torch.optim.AdamW keeps state[p]["step"] per parameter and advances it only on the steps where the parameter has a gradient, so a
-// tensor unfrozen late starts its bias correction at 1.  Tensors that took part in exactly the same step launches form a step
-// CLASS with one int64 counter in class_steps (device memory).  The byte a float4 reads selects a ROW = (hyper group, step class):
-// the rows' scalars are formed at block start from hyper[group of row] and class_steps[class of row], with the arithmetic of
-// adamw_groups_kernel expression for expression, and the element loop is that kernel's MASK instance.  The same bytes move: no
-// per-tensor id stream, no extra HBM traffic.  The row map travels as a kernel argument, checked on the host by the entry point.
-namespace {
-struct AdamwRowMap {
-  uint16_t cls[MMFN_ADAMW_MAX_ROWS];
-  uint8_t group[MMFN_ADAMW_MAX_ROWS];
-};
-
-template <bool COEF, bool AVG, bool GUARD>
-__global__ __launch_bounds__(256) void adamw_rows_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                         float* __restrict__ v, int64_t n, const uint8_t* __restrict__ row_of,
-                                                         const float* __restrict__ hyper, AdamwRowMap rows, int n_rows,
-                                                         const int64_t* __restrict__ class_steps, const float* __restrict__ coef,
-                                                         AvgArgs avg, const int32_t* __restrict__ ok) {
-  if (GUARD && !*ok) return;   // uniform over the grid: no barrier is left behind
-  __shared__ GroupScalars gs[MMFN_ADAMW_MAX_ROWS];   // 254 * 32 B = 8128 B
-  if ((int)threadIdx.x < n_rows) {
-    const float* h = hyper + rows.group[threadIdx.x] * 8;
-    const double t = (double)class_steps[rows.cls[threadIdx.x]];
-    const double lr = (double)h[0], beta1 = (double)h[1], beta2 = (double)h[2];
-    GroupScalars s;
-    s.step_size = (float)(lr / (1.0 - pow(beta1, t)));
-    s.decay = (float)(1.0 - lr * (double)h[4]);
-    s.bc2_sqrt = (float)sqrt(1.0 - pow(beta2, t));
-    s.beta1 = h[1]; s.beta2 = h[2]; s.eps = h[3]; s.grad_scale = COEF ? h[5] * *coef : h[5]; s.pad = 0.f;
-    gs[threadIdx.x] = s;
-  }
-  __syncthreads();
-  const int64_t n4 = (n + 3) >> 2;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-    const int r = row_of[i];
-    if (r >= n_rows) {   // MMFN_ADAMW_FROZEN (a byte that names no row is treated alike: it never indexes past the rows in LDS)
-      if (AVG) {
-        const f32x4 pf = *reinterpret_cast<const f32x4*>(p + i * 4);
-        f32x4 out = pf;
-        if (*avg.n_averaged != 0) out = lerp4(*reinterpret_cast<const f32x4*>(avg.avg + i * 4), pf, avg_weight(avg));
-        *reinterpret_cast<f32x4*>(avg.avg + i * 4) = out;
-      }
-      continue;
-    }
-    const GroupScalars s = gs[r];
-    f32x4 pv = *reinterpret_cast<f32x4*>(p + i * 4);
-    f32x4 gv = *reinterpret_cast<const f32x4*>(g + i * 4);
-    f32x4 mv = *reinterpret_cast<f32x4*>(m + i * 4);
-    f32x4 vv = *reinterpret_cast<f32x4*>(v + i * 4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float gg = gv[e] * s.grad_scale;
-      pv[e] *= s.decay;
-      mv[e] = mv[e] + (gg - mv[e]) * (1.0f - s.beta1);
-      vv[e] = vv[e] * s.beta2 + (1.0f - s.beta2) * gg * gg;
-      const float denom = sqrtf(vv[e]) / s.bc2_sqrt + s.eps;
-      pv[e] = pv[e] - s.step_size * (mv[e] / denom);
-    }
-    *reinterpret_cast<f32x4*>(p + i * 4) = pv;
-    *reinterpret_cast<f32x4*>(m + i * 4) = mv;
-    *reinterpret_cast<f32x4*>(v + i * 4) = vv;
-    if (AVG) {   // (the empty asm: see adamw_groups_kernel)
-      f32x4 out = pv;
-      asm volatile("" : "+v"(out));
-      pv = out;
-      if (*avg.n_averaged != 0) out = lerp4(*reinterpret_cast<const f32x4*>(avg.avg + i * 4), pv, avg_weight(avg));
-      *reinterpret_cast<f32x4*>(avg.avg + i * 4) = out;
-    }
-  }
-}
-
-using AdamwRowsKernel = decltype(&adamw_rows_kernel<false, false, false>);
-const AdamwRowsKernel kAdamwRows[8] = {   // by variant; nullptr: GUARD without COEF, which is not built
-    adamw_rows_kernel<false, false, false>, adamw_rows_kernel<true, false, false>, adamw_rows_kernel<false, true, false>,
-    adamw_rows_kernel<true, true, false>,   nullptr,                                adamw_rows_kernel<true, false, true>,
-    nullptr,                                adamw_rows_kernel<true, true, true>};
-
 // class_steps[c] += 1 for every class whose byte in `active` is set: one thread per class, plain stores
 template <bool GUARD>
 __global__ __launch_bounds__(256) void class_steps_advance_kernel(int64_t* __restrict__ class_steps, const uint8_t* __restrict__ active,
@@ -332,363 +408,94 @@ __global__ __launch_bounds__(256) void class_steps_advance_kernel(int64_t* __res
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c < n_classes && active[c]) class_steps[c] = class_steps[c] + 1;
 }
+
+constexpr int kAdamwMaxBlocks = 4096;   // beyond 4 * 256 * this many floats the grid-stride loops go round again
+int adamw_blocks(int64_t n) { return (int)std::min<int64_t>(ceil_div64(n / 4, 256), kAdamwMaxBlocks); }
+
+// the average: 16-byte aligned floats, the count (and for EMA the weight) in device memory, a known mode
+bool avg_args_ok(const AvgArgs& a) {
+  if (a.mode != MMFN_AVG_EMA && a.mode != MMFN_AVG_SWA) return false;
+  if (!a.avg || ((uintptr_t)a.avg & 15) || !a.n_averaged || ((uintptr_t)a.n_averaged & 7)) return false;
+  return a.mode != MMFN_AVG_EMA || (a.ema_w && !((uintptr_t)a.ema_w & 3));
+}
+bool flag_ok(const int32_t* ok) { return ok && !((uintptr_t)ok & 3); }   // the non-finite guard's device flag
+
+// What every entry point of the family does: the bits of `variant` (MMFN_ADAMW_COEF | _AVG | _GUARD | _MASK) are the template
+// arguments.  A set bit makes its pointers mandatory; the pointers of a clear bit are ignored.  Every pointer the launch would read
+// is there and aligned, every count in range, or nothing is launched.
+template <class Rule, class Slots>
+int launch_step(float* p, const float* g, typename Rule::State st, int64_t n, const uint8_t* slot_of, const float* hyper,
+                const SlotArgs& sa, int variant, const float* coef, const AvgArgs& avg, const int32_t* ok, void* stream) {
+  using Kernel = decltype(&optim_step_kernel<Rule, Slots, false, false, false, true>);
+#define MMFN_STEP_ROW(MASK)                                                                                                     \
+  {optim_step_kernel<Rule, Slots, false, false, false, MASK>, optim_step_kernel<Rule, Slots, true, false, false, MASK>,         \
+   optim_step_kernel<Rule, Slots, false, true, false, MASK>, optim_step_kernel<Rule, Slots, true, true, false, MASK>, nullptr,  \
+   optim_step_kernel<Rule, Slots, true, false, true, MASK>, nullptr, optim_step_kernel<Rule, Slots, true, true, true, MASK>}
+  static const Kernel kInstances[2][8] = {   // by variant; nullptr: GUARD without COEF, which is not built
+      MMFN_STEP_ROW(Slots::kMaskImplied), MMFN_STEP_ROW(true)};
+#undef MMFN_STEP_ROW
+  if (n <= 0) return 0;
+  if (variant < 0 || variant >= Slots::kVariants || !kInstances[variant >> 3][variant & 7]) return MMFN_EINVAL;
+  const bool with_coef = variant & MMFN_ADAMW_COEF, with_avg = variant & MMFN_ADAMW_AVG, guard = variant & MMFN_ADAMW_GUARD;
+  const AvgArgs a = with_avg ? avg : AvgArgs{};
+  Slots slots{};
+  if (!p || !g || !aligned16(p, g) || !st.ok() || (n & 3) || !hyper || !Slots::make(slots, sa, slot_of, variant & MMFN_ADAMW_MASK) ||
+      (with_coef && !coef) || (with_avg && !avg_args_ok(a)) || (guard && !flag_ok(ok)))
+    return MMFN_EINVAL;
+  hipLaunchKernelGGL(kInstances[variant >> 3][variant & 7], dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, st, n,
+                     slot_of, hyper, slots, with_coef ? coef : nullptr, a, guard ? ok : nullptr);
+  MMFN_LAUNCH_CHECK();
+  return 0;
+}
 }  // namespace
+
+extern "C" int mmfn_adamw_groups_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of,
+                                     const float* hyper, int n_groups, const int64_t* step, int variant, const float* coef,
+                                     float* avg, const int64_t* n_averaged, const float* ema_w, int avg_mode, const int32_t* ok,
+                                     void* stream) {
+  return launch_step<AdamwRule, GroupSlots>(p, g, {m, v}, n, group_of, hyper, {n_groups, step, nullptr, 0, 0}, variant, coef,
+                                            {avg, n_averaged, ema_w, avg_mode}, ok, stream);
+}
 
 extern "C" int mmfn_adamw_rows_f32(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* row_of, const float* hyper,
                                    int n_groups, const int32_t* rows, int n_rows, const int64_t* class_steps, int n_classes,
                                    int variant, const float* coef, float* avg, const int64_t* n_averaged, const float* ema_w,
                                    int avg_mode, const int32_t* ok, void* stream) {
-  if (n <= 0) return 0;
-  if (variant < 0 || variant >= 8 || !kAdamwRows[variant]) return MMFN_EINVAL;
-  const bool with_coef = variant & MMFN_ADAMW_COEF, with_avg = variant & MMFN_ADAMW_AVG, guard = variant & MMFN_ADAMW_GUARD;
-  const AvgArgs a = with_avg ? AvgArgs{avg, n_averaged, ema_w, avg_mode} : AvgArgs{};
-  if (!p || !g || !m || !v || !row_of || !rows || n_rows < 1 || n_rows > MMFN_ADAMW_MAX_ROWS || n_classes < 1 || n_classes > 65536 ||
-      ((uintptr_t)class_steps & 7) || !adamw_args_ok(p, g, m, v, n, hyper, n_groups, class_steps) || (with_coef && !coef) ||
-      (with_avg && !avg_args_ok(a)) || (guard && !flag_ok(ok)))
-    return MMFN_EINVAL;
-  AdamwRowMap map{};
-  for (int r = 0; r < n_rows; ++r) {   // rows: HOST memory, [n_rows][2] = (group, class), every entry inside its table
-    const int32_t grp = rows[2 * r], cls = rows[2 * r + 1];
-    if (grp < 0 || grp >= n_groups || cls < 0 || cls >= n_classes) return MMFN_EINVAL;
-    map.group[r] = (uint8_t)grp;
-    map.cls[r] = (uint16_t)cls;
-  }
-  hipLaunchKernelGGL(kAdamwRows[variant], dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, row_of, hyper, map,
-                     n_rows, class_steps, with_coef ? coef : nullptr, a, guard ? ok : nullptr);
-  MMFN_LAUNCH_CHECK();
-  return 0;
+  return launch_step<AdamwRule, RowSlots>(p, g, {m, v}, n, row_of, hyper, {n_groups, class_steps, rows, n_rows, n_classes}, variant,
+                                          coef, {avg, n_averaged, ema_w, avg_mode}, ok, stream);
 }
-
-// ---- amsgrad (torch.optim.AdamW(amsgrad=True), the single-tensor non-capturable form) ------------------------------------------
-// A fifth stream vmax holds the running maximum of the second moment: vmax = maximum(vmax, v_new), and the denominator is built
-// from sqrtf(vmax) instead of sqrtf(v_new).  amsgrad is a per-group property: hyper[group][7] != 0 switches it on, and a float4 of
-// a group without it neither loads nor stores vmax and gets the bits of adamw_groups_kernel.  Kernels of their own and not a
-// branch of the ones above, which keep their code.  36 B per parameter of an amsgrad group instead of 28.
-namespace {
-// one group's (one row's) scalars with the expressions of adamw_groups_kernel; pad carries the amsgrad flag
-template <bool COEF>
-__device__ inline GroupScalars ams_scalars(const float* __restrict__ h, double t, const float* __restrict__ coef) {
-  const double lr = (double)h[0], beta1 = (double)h[1], beta2 = (double)h[2];
-  GroupScalars s;
-  s.step_size = (float)(lr / (1.0 - pow(beta1, t)));
-  s.decay = (float)(1.0 - lr * (double)h[4]);
-  s.bc2_sqrt = (float)sqrt(1.0 - pow(beta2, t));
-  s.beta1 = h[1]; s.beta2 = h[2]; s.eps = h[3]; s.grad_scale = COEF ? h[5] * *coef : h[5]; s.pad = h[7];
-  return s;
-}
-
-// torch.maximum: NaN when either operand is NaN (fmaxf would drop it)
-__device__ inline float max_nan(float a, float b) { return (a == a && !(b <= a)) ? b : a; }
-
-// One float4 of the step; returns the new parameter.  The element arithmetic is written out operation by operation, with the
-// contractions the compiler chose for adamw_groups_kernel as explicit fmaf calls and contraction switched off for the rest, so
-// that the bits do not depend on what else reads the values here: g * grad_scale - m is one fma, so are the two moment updates
-// and p * decay - step_size * q.
-__device__ inline f32x4 adamw_ams_float4(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                         float* __restrict__ v, float* __restrict__ vmax, int64_t i, const GroupScalars& s) {
-#pragma clang fp contract(off)
-  const bool ams = s.pad != 0.f;
-  f32x4 pv = *reinterpret_cast<f32x4*>(p + i * 4);
-  const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i * 4);
-  f32x4 mv = *reinterpret_cast<f32x4*>(m + i * 4);
-  f32x4 vv = *reinterpret_cast<f32x4*>(v + i * 4);
-  f32x4 xv = vv;
-  if (ams) xv = *reinterpret_cast<f32x4*>(vmax + i * 4);
-  const float omb1 = 1.0f - s.beta1, omb2 = 1.0f - s.beta2;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float gg = gv[e] * s.grad_scale;
-    mv[e] = __builtin_fmaf(omb1, __builtin_fmaf(gv[e], s.grad_scale, -mv[e]), mv[e]);
-    vv[e] = __builtin_fmaf(s.beta2, vv[e], gg * (omb2 * gg));
-    xv[e] = ams ? max_nan(xv[e], vv[e]) : vv[e];
-    const float denom = sqrtf(xv[e]) / s.bc2_sqrt + s.eps;
-    pv[e] = __builtin_fmaf(s.decay, pv[e], -(s.step_size * (mv[e] / denom)));
-  }
-  *reinterpret_cast<f32x4*>(p + i * 4) = pv;
-  *reinterpret_cast<f32x4*>(m + i * 4) = mv;
-  *reinterpret_cast<f32x4*>(v + i * 4) = vv;
-  if (ams) *reinterpret_cast<f32x4*>(vmax + i * 4) = xv;
-  return pv;
-}
-
-// the average's update of one float4 from the parameter pf, as the AVG branches of adamw_groups_kernel do it
-__device__ inline void avg_float4(const AvgArgs& avg, int64_t i, f32x4 pf) {
-  f32x4 out = pf;
-  if (*avg.n_averaged != 0) out = lerp4(*reinterpret_cast<const f32x4*>(avg.avg + i * 4), pf, avg_weight(avg));
-  *reinterpret_cast<f32x4*>(avg.avg + i * 4) = out;
-}
-
-// COEF / AVG / GUARD / MASK as in adamw_groups_kernel
-template <bool COEF, bool AVG, bool GUARD, bool MASK>
-__global__ __launch_bounds__(256) void adamw_groups_ams_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                               float* __restrict__ v, float* __restrict__ vmax, int64_t n,
-                                                               const uint8_t* __restrict__ group_of, const float* __restrict__ hyper,
-                                                               int n_groups, const int64_t* __restrict__ step,
-                                                               const float* __restrict__ coef, AvgArgs avg,
-                                                               const int32_t* __restrict__ ok) {
-  if (GUARD && !*ok) return;   // uniform over the grid: no barrier is left behind
-  __shared__ GroupScalars gs[MMFN_ADAMW_MAX_GROUPS];
-  if ((int)threadIdx.x < n_groups) gs[threadIdx.x] = ams_scalars<COEF>(hyper + threadIdx.x * 8, (double)*step, coef);
-  __syncthreads();
-  const int64_t n4 = (n + 3) >> 2;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-    if (MASK && group_of[i] == MMFN_ADAMW_FROZEN) {   // frozen: none of p / m / v / vmax, p alone for the average
-      if (AVG) avg_float4(avg, i, *reinterpret_cast<const f32x4*>(p + i * 4));
-      continue;
-    }
-    f32x4 pv = adamw_ams_float4(p, g, m, v, vmax, i, gs[group_of ? group_of[i] : 0]);
-    if (AVG) {
-      asm volatile("" : "+v"(pv));   // (the new parameter is opaque to the lerp: see adamw_groups_kernel)
-      avg_float4(avg, i, pv);
-    }
-  }
-}
-
-template <bool COEF, bool AVG, bool GUARD>
-__global__ __launch_bounds__(256) void adamw_rows_ams_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                             float* __restrict__ v, float* __restrict__ vmax, int64_t n,
-                                                             const uint8_t* __restrict__ row_of, const float* __restrict__ hyper,
-                                                             AdamwRowMap rows, int n_rows, const int64_t* __restrict__ class_steps,
-                                                             const float* __restrict__ coef, AvgArgs avg,
-                                                             const int32_t* __restrict__ ok) {
-  if (GUARD && !*ok) return;
-  __shared__ GroupScalars gs[MMFN_ADAMW_MAX_ROWS];
-  if ((int)threadIdx.x < n_rows)
-    gs[threadIdx.x] = ams_scalars<COEF>(hyper + rows.group[threadIdx.x] * 8, (double)class_steps[rows.cls[threadIdx.x]], coef);
-  __syncthreads();
-  const int64_t n4 = (n + 3) >> 2;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-    const int r = row_of[i];
-    if (r >= n_rows) {   // MMFN_ADAMW_FROZEN, or a byte that names no row
-      if (AVG) avg_float4(avg, i, *reinterpret_cast<const f32x4*>(p + i * 4));
-      continue;
-    }
-    f32x4 pv = adamw_ams_float4(p, g, m, v, vmax, i, gs[r]);
-    if (AVG) {
-      asm volatile("" : "+v"(pv));
-      avg_float4(avg, i, pv);
-    }
-  }
-}
-
-using AdamwGroupsAmsKernel = decltype(&adamw_groups_ams_kernel<false, false, false, false>);
-#define MMFN_ADAMW_AMS_ROW(MASK)                                                                                                \
-  adamw_groups_ams_kernel<false, false, false, MASK>, adamw_groups_ams_kernel<true, false, false, MASK>,                        \
-      adamw_groups_ams_kernel<false, true, false, MASK>, adamw_groups_ams_kernel<true, true, false, MASK>, nullptr,             \
-      adamw_groups_ams_kernel<true, false, true, MASK>, nullptr, adamw_groups_ams_kernel<true, true, true, MASK>
-const AdamwGroupsAmsKernel kAdamwGroupsAms[16] = {MMFN_ADAMW_AMS_ROW(false), MMFN_ADAMW_AMS_ROW(true)};   // as kAdamwGroups
-#undef MMFN_ADAMW_AMS_ROW
-
-using AdamwRowsAmsKernel = decltype(&adamw_rows_ams_kernel<false, false, false>);
-const AdamwRowsAmsKernel kAdamwRowsAms[8] = {   // as kAdamwRows
-    adamw_rows_ams_kernel<false, false, false>, adamw_rows_ams_kernel<true, false, false>, adamw_rows_ams_kernel<false, true, false>,
-    adamw_rows_ams_kernel<true, true, false>,   nullptr,                                    adamw_rows_ams_kernel<true, false, true>,
-    nullptr,                                    adamw_rows_ams_kernel<true, true, true>};
-
-bool vmax_ok(const float* p, const float* g, const float* m, const float* v, const float* vmax) {
-  return p && g && m && v && vmax && !((uintptr_t)vmax & 15);
-}
-}  // namespace
 
 extern "C" int mmfn_adamw_groups_ams_f32(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, const uint8_t* group_of,
                                          const float* hyper, int n_groups, const int64_t* step, int variant, const float* coef,
                                          float* avg, const int64_t* n_averaged, const float* ema_w, int avg_mode, const int32_t* ok,
                                          void* stream) {
-  if (n <= 0) return 0;
-  if (variant < 0 || variant >= 16 || !kAdamwGroupsAms[variant]) return MMFN_EINVAL;
-  const bool with_coef = variant & MMFN_ADAMW_COEF, with_avg = variant & MMFN_ADAMW_AVG, guard = variant & MMFN_ADAMW_GUARD;
-  const bool mask = variant & MMFN_ADAMW_MASK;
-  const AvgArgs a = with_avg ? AvgArgs{avg, n_averaged, ema_w, avg_mode} : AvgArgs{};
-  if (!vmax_ok(p, g, m, v, vmax) || ((uintptr_t)step & 7) || !adamw_args_ok(p, g, m, v, n, hyper, n_groups, step) ||
-      (with_coef && !coef) || (with_avg && !avg_args_ok(a)) || (guard && !flag_ok(ok)) || (mask && !group_of))
-    return MMFN_EINVAL;
-  hipLaunchKernelGGL(kAdamwGroupsAms[variant], dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, vmax, n, group_of,
-                     hyper, n_groups, step, with_coef ? coef : nullptr, a, guard ? ok : nullptr);
-  MMFN_LAUNCH_CHECK();
-  return 0;
+  return launch_step<AdamwAmsRule, GroupSlots>(p, g, {m, v, vmax}, n, group_of, hyper, {n_groups, step, nullptr, 0, 0}, variant,
+                                               coef, {avg, n_averaged, ema_w, avg_mode}, ok, stream);
 }
 
 extern "C" int mmfn_adamw_rows_ams_f32(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, const uint8_t* row_of,
                                        const float* hyper, int n_groups, const int32_t* rows, int n_rows, const int64_t* class_steps,
                                        int n_classes, int variant, const float* coef, float* avg, const int64_t* n_averaged,
                                        const float* ema_w, int avg_mode, const int32_t* ok, void* stream) {
-  if (n <= 0) return 0;
-  if (variant < 0 || variant >= 8 || !kAdamwRowsAms[variant]) return MMFN_EINVAL;
-  const bool with_coef = variant & MMFN_ADAMW_COEF, with_avg = variant & MMFN_ADAMW_AVG, guard = variant & MMFN_ADAMW_GUARD;
-  const AvgArgs a = with_avg ? AvgArgs{avg, n_averaged, ema_w, avg_mode} : AvgArgs{};
-  if (!vmax_ok(p, g, m, v, vmax) || !row_of || !rows || n_rows < 1 || n_rows > MMFN_ADAMW_MAX_ROWS || n_classes < 1 ||
-      n_classes > 65536 || ((uintptr_t)class_steps & 7) || !adamw_args_ok(p, g, m, v, n, hyper, n_groups, class_steps) ||
-      (with_coef && !coef) || (with_avg && !avg_args_ok(a)) || (guard && !flag_ok(ok)))
-    return MMFN_EINVAL;
-  AdamwRowMap map{};
-  for (int r = 0; r < n_rows; ++r) {   // rows: HOST memory, [n_rows][2] = (group, class), every entry inside its table
-    const int32_t grp = rows[2 * r], cls = rows[2 * r + 1];
-    if (grp < 0 || grp >= n_groups || cls < 0 || cls >= n_classes) return MMFN_EINVAL;
-    map.group[r] = (uint8_t)grp;
-    map.cls[r] = (uint16_t)cls;
-  }
-  hipLaunchKernelGGL(kAdamwRowsAms[variant], dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, vmax, n, row_of,
-                     hyper, map, n_rows, class_steps, with_coef ? coef : nullptr, a, guard ? ok : nullptr);
-  MMFN_LAUNCH_CHECK();
-  return 0;
+  return launch_step<AdamwAmsRule, RowSlots>(p, g, {m, v, vmax}, n, row_of, hyper, {n_groups, class_steps, rows, n_rows, n_classes},
+                                             variant, coef, {avg, n_averaged, ema_w, avg_mode}, ok, stream);
 }
-
-// ---- momentum SGD (torch.optim.SGD, the single-tensor form) on the machinery of the grouped AdamW launches -------------------
-// One state stream buf (torch's momentum_buffer) instead of m and v: 20 B per parameter (read p, g, buf; write p, buf), 12 B for a
-// float4 of a group with momentum 0, which neither loads nor stores buf.  hyper row: {lr, momentum, dampening, nesterov,
-// weight_decay, grad_scale, max_norm, 0}.  Per element
-//     d   = g * grad_scale + weight_decay * p          (coupled decay)
-//     buf = first ? d : momentum * buf + (1 - dampening) * d
-//     p   = p - lr * (nesterov ? d + momentum * buf : buf)
-// first: the tensor's step count after the advance is 1 (torch: momentum_buffer is None) - *step for the groups kernel, the
-// row's class counter for the rows kernel.  Kernels of their own: the AdamW launches keep their code.
-namespace {
-struct SgdScalars { float lr, momentum, omd, wd, grad_scale, nesterov, first, pad; };
-
-template <bool COEF>
-__device__ inline SgdScalars sgd_scalars(const float* __restrict__ h, int64_t t, const float* __restrict__ coef) {
-  SgdScalars s;
-  s.lr = h[0]; s.momentum = h[1];
-  s.omd = (float)(1.0 - (double)h[2]);   // in fp64 like torch's Python-side 1 - dampening, rounded once
-  s.wd = h[4]; s.grad_scale = COEF ? h[5] * *coef : h[5];
-  s.nesterov = h[3]; s.first = t == 1 ? 1.f : 0.f; s.pad = 0.f;
-  return s;
-}
-
-// One float4 of the step; returns the new parameter.  Written operation by operation with explicit fmaf calls and contraction
-// switched off for the rest (as adamw_ams_float4), so that the bits do not depend on the instance around it.
-__device__ inline f32x4 sgd_float4(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, int64_t i,
-                                   const SgdScalars& s) {
-#pragma clang fp contract(off)
-  const bool mom = s.momentum != 0.f, first = s.first != 0.f, nesterov = s.nesterov != 0.f, decay = s.wd != 0.f;
-  f32x4 pv = *reinterpret_cast<f32x4*>(p + i * 4);
-  const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i * 4);
-  f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-  if (mom && !first) bv = *reinterpret_cast<f32x4*>(buf + i * 4);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float gg = gv[e] * s.grad_scale;
-    const float d = decay ? __builtin_fmaf(s.wd, pv[e], gg) : gg;
-    float u = d;
-    if (mom) {
-      bv[e] = first ? d : __builtin_fmaf(s.omd, d, s.momentum * bv[e]);
-      u = nesterov ? __builtin_fmaf(s.momentum, bv[e], d) : bv[e];
-    }
-    pv[e] = __builtin_fmaf(-s.lr, u, pv[e]);
-  }
-  *reinterpret_cast<f32x4*>(p + i * 4) = pv;
-  if (mom) *reinterpret_cast<f32x4*>(buf + i * 4) = bv;
-  return pv;
-}
-
-// COEF / AVG / GUARD / MASK as in adamw_groups_kernel
-template <bool COEF, bool AVG, bool GUARD, bool MASK>
-__global__ __launch_bounds__(256) void sgd_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
-                                                         int64_t n, const uint8_t* __restrict__ group_of,
-                                                         const float* __restrict__ hyper, int n_groups,
-                                                         const int64_t* __restrict__ step, const float* __restrict__ coef, AvgArgs avg,
-                                                         const int32_t* __restrict__ ok) {
-  if (GUARD && !*ok) return;   // uniform over the grid: no barrier is left behind
-  __shared__ SgdScalars gs[MMFN_ADAMW_MAX_GROUPS];
-  if ((int)threadIdx.x < n_groups) gs[threadIdx.x] = sgd_scalars<COEF>(hyper + threadIdx.x * 8, *step, coef);
-  __syncthreads();
-  const int64_t n4 = (n + 3) >> 2;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-    if (MASK && group_of[i] == MMFN_ADAMW_FROZEN) {   // frozen: neither p nor buf, p alone for the average
-      if (AVG) avg_float4(avg, i, *reinterpret_cast<const f32x4*>(p + i * 4));
-      continue;
-    }
-    // (a byte that names no group of the table reads group 0: it never indexes past the scalars in LDS)
-    const int grp = group_of ? group_of[i] : 0;
-    f32x4 pv = sgd_float4(p, g, buf, i, gs[grp < n_groups ? grp : 0]);
-    if (AVG) {
-      asm volatile("" : "+v"(pv));   // (the new parameter is opaque to the lerp: see adamw_groups_kernel)
-      avg_float4(avg, i, pv);
-    }
-  }
-}
-
-template <bool COEF, bool AVG, bool GUARD>
-__global__ __launch_bounds__(256) void sgd_rows_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
-                                                       int64_t n, const uint8_t* __restrict__ row_of, const float* __restrict__ hyper,
-                                                       AdamwRowMap rows, int n_rows, const int64_t* __restrict__ class_steps,
-                                                       const float* __restrict__ coef, AvgArgs avg, const int32_t* __restrict__ ok) {
-  if (GUARD && !*ok) return;
-  __shared__ SgdScalars gs[MMFN_ADAMW_MAX_ROWS];   // 254 * 32 B = 8128 B
-  if ((int)threadIdx.x < n_rows)
-    gs[threadIdx.x] = sgd_scalars<COEF>(hyper + rows.group[threadIdx.x] * 8, class_steps[rows.cls[threadIdx.x]], coef);
-  __syncthreads();
-  const int64_t n4 = (n + 3) >> 2;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-    const int r = row_of[i];
-    if (r >= n_rows) {   // MMFN_ADAMW_FROZEN, or a byte that names no row
-      if (AVG) avg_float4(avg, i, *reinterpret_cast<const f32x4*>(p + i * 4));
-      continue;
-    }
-    f32x4 pv = sgd_float4(p, g, buf, i, gs[r]);
-    if (AVG) {
-      asm volatile("" : "+v"(pv));
-      avg_float4(avg, i, pv);
-    }
-  }
-}
-
-using SgdGroupsKernel = decltype(&sgd_groups_kernel<false, false, false, false>);
-#define MMFN_SGD_ROW(MASK)                                                                                                      \
-  sgd_groups_kernel<false, false, false, MASK>, sgd_groups_kernel<true, false, false, MASK>,                                    \
-      sgd_groups_kernel<false, true, false, MASK>, sgd_groups_kernel<true, true, false, MASK>, nullptr,                         \
-      sgd_groups_kernel<true, false, true, MASK>, nullptr, sgd_groups_kernel<true, true, true, MASK>
-const SgdGroupsKernel kSgdGroups[16] = {MMFN_SGD_ROW(false), MMFN_SGD_ROW(true)};   // as kAdamwGroups
-#undef MMFN_SGD_ROW
-
-using SgdRowsKernel = decltype(&sgd_rows_kernel<false, false, false>);
-const SgdRowsKernel kSgdRows[8] = {   // as kAdamwRows
-    sgd_rows_kernel<false, false, false>, sgd_rows_kernel<true, false, false>, sgd_rows_kernel<false, true, false>,
-    sgd_rows_kernel<true, true, false>,   nullptr,                              sgd_rows_kernel<true, false, true>,
-    nullptr,                              sgd_rows_kernel<true, true, true>};
-}  // namespace
 
 extern "C" int mmfn_sgd_groups_f32(float* p, const float* g, float* buf, int64_t n, const uint8_t* group_of, const float* hyper,
                                    int n_groups, const int64_t* step, int variant, const float* coef, float* avg,
                                    const int64_t* n_averaged, const float* ema_w, int avg_mode, const int32_t* ok, void* stream) {
-  if (n <= 0) return 0;
-  if (variant < 0 || variant >= 16 || !kSgdGroups[variant]) return MMFN_EINVAL;
-  const bool with_coef = variant & MMFN_ADAMW_COEF, with_avg = variant & MMFN_ADAMW_AVG, guard = variant & MMFN_ADAMW_GUARD;
-  const bool mask = variant & MMFN_ADAMW_MASK;
-  const AvgArgs a = with_avg ? AvgArgs{avg, n_averaged, ema_w, avg_mode} : AvgArgs{};
-  if (!p || !g || !buf || ((uintptr_t)step & 7) || !adamw_args_ok(p, g, buf, buf, n, hyper, n_groups, step) ||
-      (with_coef && !coef) || (with_avg && !avg_args_ok(a)) || (guard && !flag_ok(ok)) || (mask && !group_of))
-    return MMFN_EINVAL;
-  hipLaunchKernelGGL(kSgdGroups[variant], dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, buf, n, group_of, hyper,
-                     n_groups, step, with_coef ? coef : nullptr, a, guard ? ok : nullptr);
-  MMFN_LAUNCH_CHECK();
-  return 0;
+  return launch_step<SgdRule, GroupSlots>(p, g, {buf}, n, group_of, hyper, {n_groups, step, nullptr, 0, 0}, variant, coef,
+                                          {avg, n_averaged, ema_w, avg_mode}, ok, stream);
 }
 
 extern "C" int mmfn_sgd_rows_f32(float* p, const float* g, float* buf, int64_t n, const uint8_t* row_of, const float* hyper,
                                  int n_groups, const int32_t* rows, int n_rows, const int64_t* class_steps, int n_classes, int variant,
                                  const float* coef, float* avg, const int64_t* n_averaged, const float* ema_w, int avg_mode,
                                  const int32_t* ok, void* stream) {
-  if (n <= 0) return 0;
-  if (variant < 0 || variant >= 8 || !kSgdRows[variant]) return MMFN_EINVAL;
-  const bool with_coef = variant & MMFN_ADAMW_COEF, with_avg = variant & MMFN_ADAMW_AVG, guard = variant & MMFN_ADAMW_GUARD;
-  const AvgArgs a = with_avg ? AvgArgs{avg, n_averaged, ema_w, avg_mode} : AvgArgs{};
-  if (!p || !g || !buf || !row_of || !rows || n_rows < 1 || n_rows > MMFN_ADAMW_MAX_ROWS || n_classes < 1 || n_classes > 65536 ||
-      ((uintptr_t)class_steps & 7) || !adamw_args_ok(p, g, buf, buf, n, hyper, n_groups, class_steps) || (with_coef && !coef) ||
-      (with_avg && !avg_args_ok(a)) || (guard && !flag_ok(ok)))
-    return MMFN_EINVAL;
-  AdamwRowMap map{};
-  for (int r = 0; r < n_rows; ++r) {   // rows: HOST memory, [n_rows][2] = (group, class), every entry inside its table
-    const int32_t grp = rows[2 * r], cls = rows[2 * r + 1];
-    if (grp < 0 || grp >= n_groups || cls < 0 || cls >= n_classes) return MMFN_EINVAL;
-    map.group[r] = (uint8_t)grp;
-    map.cls[r] = (uint16_t)cls;
-  }
-  hipLaunchKernelGGL(kSgdRows[variant], dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, buf, n, row_of, hyper, map,
-                     n_rows, class_steps, with_coef ? coef : nullptr, a, guard ? ok : nullptr);
-  MMFN_LAUNCH_CHECK();
-  return 0;
+  return launch_step<SgdRule, RowSlots>(p, g, {buf}, n, row_of, hyper, {n_groups, class_steps, rows, n_rows, n_classes}, variant, coef,
+                                        {avg, n_averaged, ema_w, avg_mode}, ok, stream);
 }
+
 
 extern "C" int mmfn_adamw_max_blocks(void) { return kAdamwMaxBlocks; }
 

@@ -2275,32 +2275,26 @@ class Engine(object):
         # amsgrad in some group of the table as set_hyper wrote it: the launch that also carries max_exp_avg_sq (None: the plain one)
         vmax = L.max_exp_avg_sq if any(self._hyper_flags[:n_groups]) else None
         if self.opt_kind == "sgd":
-            # momentum SGD: the same three instances over (p, g, momentum buffer = exp_avg); a tensor's first step is the one
-            # its count reads 1 at, which the step classes make per tensor
+            # momentum SGD: the same launches over (p, g, momentum buffer = exp_avg); a tensor's first step is the one its count
+            # reads 1 at, which the step classes make per tensor
             if vmax is not None:
                 raise ValueError("amsgrad flags in the hyper table of an SGD step")
-            if not self.classes.uniform():
-                row_of, rows = self._rows(n_groups)
-                ops.sgd_rows(L.params, L.grads, L.exp_avg, self._class_steps, self.classes.n_classes, self.opt_hyper, n_groups,
-                             row_of, rows, n=L.tail, coef=coef, avg=avg, ok=ok)
-            elif self.frozen:
-                ops.sgd_groups(L.params, L.grads, L.exp_avg, self.step_count, self.opt_hyper, n_groups,
-                               group_of=self._group_table(n_groups), n=L.tail, coef=coef, avg=avg, ok=ok, mask=True)
-            else:
-                ops.sgd_groups(L.params, L.grads, L.exp_avg, self.step_count, self.opt_hyper, n_groups,
-                               group_of=self.opt_group_of if n_groups > 1 else None, n=L.tail, coef=coef, avg=avg, ok=ok)
-        elif not self.classes.uniform():
-            # a tensor that steps has a count of its own: the instance whose bias corrections follow the step classes
-            row_of, rows = self._rows(n_groups)
-            ops.adamw_rows(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self._class_steps, self.classes.n_classes, self.opt_hyper,
-                           n_groups, row_of, rows, n=L.tail, coef=coef, avg=avg, ok=ok, vmax=vmax)
-        elif self.frozen:
-            # the masked instance: frozen float4s keep parameter, moments and decay untouched (the average still follows them)
-            ops.adamw_groups(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self.step_count, self.opt_hyper, n_groups,
-                             group_of=self._group_table(n_groups), n=L.tail, coef=coef, avg=avg, ok=ok, mask=True, vmax=vmax)
+            groups, rows, state = ops.sgd_groups, ops.sgd_rows, (L.exp_avg,)
+            kw = dict(n=L.tail, coef=coef, avg=avg, ok=ok)
         else:
-            ops.adamw_groups(L.params, L.grads, L.exp_avg, L.exp_avg_sq, self.step_count, self.opt_hyper, n_groups,
-                             group_of=self.opt_group_of if n_groups > 1 else None, n=L.tail, coef=coef, avg=avg, ok=ok, vmax=vmax)
+            groups, rows, state = ops.adamw_groups, ops.adamw_rows, (L.exp_avg, L.exp_avg_sq)
+            kw = dict(n=L.tail, coef=coef, avg=avg, ok=ok, vmax=vmax)
+        if not self.classes.uniform():
+            # a tensor that steps has a count of its own: the launch whose scalars follow the step classes
+            row_of, row_map = self._rows(n_groups)
+            rows(L.params, L.grads, *state, self._class_steps, self.classes.n_classes, self.opt_hyper, n_groups, row_of, row_map, **kw)
+        elif self.frozen:
+            # the masked instance: frozen float4s keep parameter, state and decay untouched (the average still follows them)
+            groups(L.params, L.grads, *state, self.step_count, self.opt_hyper, n_groups, group_of=self._group_table(n_groups),
+                   mask=True, **kw)
+        else:
+            groups(L.params, L.grads, *state, self.step_count, self.opt_hyper, n_groups,
+                   group_of=self.opt_group_of if n_groups > 1 else None, **kw)
         self.never_stepped = self.frozen if self.never_stepped is None else (self.never_stepped & self.frozen)
         self.classes.launched()
         if a is not None:

@@ -1210,9 +1210,50 @@ def adamw_max_blocks():
     return int(lib().mmfn_adamw_max_blocks())
 
 
+ADAMW_MAX_ROWS = 254   # mirror include/mmfn_hip.h
+
+
 def _check_vmax(vmax, p, n):
     if vmax.dtype != torch.float32 or vmax.device != p.device or vmax.numel() < n:
         raise ValueError("vmax (max_exp_avg_sq) is a float32 tensor on the parameters' device with one entry per parameter of the range")
+
+
+def _check_momentum_buffer(buf, p, n):
+    if buf is None or buf.dtype != torch.float32 or buf.device != p.device or buf.numel() < n:
+        raise ValueError("buf (momentum_buffer) is a float32 tensor on the parameters' device with one entry per parameter of the range")
+
+
+# What the four fronts of the step family (adamw_groups / adamw_rows / sgd_groups / sgd_rows) share; rule: "AdamW" or "SGD", the
+# word their error messages name the launch by.
+def _check_group_table(rule, group_of, n):
+    if group_of is None or group_of.dtype != torch.uint8 or group_of.numel() * 4 < n:
+        raise ValueError("the masked %s launch needs a uint8 group table with one byte per float4 of the range" % rule)
+
+
+def _check_rows(rule, row_of, rows, class_steps, n_classes, n):
+    if row_of is None or row_of.dtype != torch.uint8 or row_of.numel() * 4 < n:
+        raise ValueError("the %s launch with step classes needs a uint8 row table with one byte per float4 of the range" % rule)
+    if rows.device.type != "cpu" or rows.dtype != torch.int32 or rows.dim() != 2 or rows.shape[1] != 2 or not rows.is_contiguous():
+        raise ValueError("rows is a contiguous CPU int32 tensor [n_rows, 2] of (group, class)")
+    if not 1 <= rows.shape[0] <= ADAMW_MAX_ROWS:
+        raise ValueError("%d (group, step class) rows: the %s launch holds at most %d" % (rows.shape[0], rule, ADAMW_MAX_ROWS))
+    if class_steps.dtype != torch.int64 or class_steps.numel() < n_classes:
+        raise ValueError("class_steps holds %d %s counters, the launch reads %d int64" % (class_steps.numel(), class_steps.dtype, n_classes))
+
+
+def _avg_args(avg, n):
+    """The average's four C arguments from the fronts' avg tuple (None: no average)."""
+    a, n_averaged, ema_weight, mode = (None, None, None, 0) if avg is None else avg
+    if a is not None and a.numel() < n:
+        raise ValueError("average holds %d floats, the step covers %d" % (a.numel(), n))
+    return ptr(a), ptr(n_averaged), ptr(ema_weight), int(mode)
+
+
+def _step_variant(rule, coef, avg, ok, mask=False):
+    if ok is not None and coef is None:
+        raise ValueError("the guarded %s launch is the coefficient instance: pass coef" % rule)
+    variant = sum(bit for bit, arg in ((ADAMW_COEF, coef), (ADAMW_AVG, avg), (ADAMW_GUARD, ok)) if arg is not None)
+    return variant | ADAMW_MASK if mask else variant
 
 
 def adamw_groups(p, g, m, v, step, hyper, n_groups, group_of=None, n=None, coef=None, avg=None, ok=None, mask=False, vmax=None):
@@ -1223,26 +1264,17 @@ def adamw_groups(p, g, m, v, step, hyper, n_groups, group_of=None, n=None, coef=
     updated from p); group_of is then mandatory, also with one group.  vmax: the amsgrad launch (mmfn_adamw_groups_ams_f32) - the
     running maximum of v, read and written for the groups whose hyper row has a non-zero last float; None: the launch without."""
     n = p.numel() if n is None else n
-    if mask and (group_of is None or group_of.dtype != torch.uint8 or group_of.numel() * 4 < n):
-        raise ValueError("the masked AdamW launch needs a uint8 group table with one byte per float4 of the range")
-    a, n_averaged, ema_weight, mode = (None, None, None, 0) if avg is None else avg
-    if a is not None and a.numel() < n:
-        raise ValueError("average holds %d floats, the step covers %d" % (a.numel(), n))
-    if ok is not None and coef is None:
-        raise ValueError("the guarded AdamW launch is the coefficient instance: pass coef")
-    variant = sum(bit for bit, arg in ((ADAMW_COEF, coef), (ADAMW_AVG, avg), (ADAMW_GUARD, ok)) if arg is not None)
     if mask:
-        variant |= ADAMW_MASK
+        _check_group_table("AdamW", group_of, n)
+    avg_args = _avg_args(avg, n)
+    variant = _step_variant("AdamW", coef, avg, ok, mask)
     if vmax is not None:
         _check_vmax(vmax, p, n)
         _call("mmfn_adamw_groups_ams_f32", ptr(p), ptr(g), ptr(m), ptr(v), ptr(vmax), n, ptr(group_of), ptr(hyper), n_groups, ptr(step),
-              variant, ptr(coef), ptr(a), ptr(n_averaged), ptr(ema_weight), int(mode), ptr(ok), stream())
+              variant, ptr(coef), *avg_args, ptr(ok), stream())
         return
     _call("mmfn_adamw_groups_f32", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(group_of), ptr(hyper), n_groups, ptr(step), variant,
-          ptr(coef), ptr(a), ptr(n_averaged), ptr(ema_weight), int(mode), ptr(ok), stream())
-
-
-ADAMW_MAX_ROWS = 254   # mirror include/mmfn_hip.h
+          ptr(coef), *avg_args, ptr(ok), stream())
 
 
 def adamw_rows(p, g, m, v, class_steps, n_classes, hyper, n_groups, row_of, rows, n=None, coef=None, avg=None, ok=None, vmax=None):
@@ -1250,33 +1282,16 @@ def adamw_rows(p, g, m, v, class_steps, n_classes, hyper, n_groups, row_of, rows
     `rows` (a CPU int32 tensor [n_rows, 2] of (hyper group, step class)); a row's bias corrections come from class_steps[class]
     (int64, device).  coef / avg / ok / vmax as in adamw_groups; frozen float4s as in its masked launch."""
     n = p.numel() if n is None else n
-    if row_of is None or row_of.dtype != torch.uint8 or row_of.numel() * 4 < n:
-        raise ValueError("the AdamW launch with step classes needs a uint8 row table with one byte per float4 of the range")
-    if rows.device.type != "cpu" or rows.dtype != torch.int32 or rows.dim() != 2 or rows.shape[1] != 2 or not rows.is_contiguous():
-        raise ValueError("rows is a contiguous CPU int32 tensor [n_rows, 2] of (group, class)")
-    if not 1 <= rows.shape[0] <= ADAMW_MAX_ROWS:
-        raise ValueError("%d (group, step class) rows: the AdamW launch holds at most %d" % (rows.shape[0], ADAMW_MAX_ROWS))
-    if class_steps.dtype != torch.int64 or class_steps.numel() < n_classes:
-        raise ValueError("class_steps holds %d %s counters, the launch reads %d int64" % (class_steps.numel(), class_steps.dtype, n_classes))
-    a, n_averaged, ema_weight, mode = (None, None, None, 0) if avg is None else avg
-    if a is not None and a.numel() < n:
-        raise ValueError("average holds %d floats, the step covers %d" % (a.numel(), n))
-    if ok is not None and coef is None:
-        raise ValueError("the guarded AdamW launch is the coefficient instance: pass coef")
-    variant = sum(bit for bit, arg in ((ADAMW_COEF, coef), (ADAMW_AVG, avg), (ADAMW_GUARD, ok)) if arg is not None)
+    _check_rows("AdamW", row_of, rows, class_steps, n_classes, n)
+    avg_args = _avg_args(avg, n)
+    variant = _step_variant("AdamW", coef, avg, ok)
     if vmax is not None:
         _check_vmax(vmax, p, n)
         _call("mmfn_adamw_rows_ams_f32", ptr(p), ptr(g), ptr(m), ptr(v), ptr(vmax), n, ptr(row_of), ptr(hyper), n_groups, rows.data_ptr(),
-              rows.shape[0], ptr(class_steps), n_classes, variant, ptr(coef), ptr(a), ptr(n_averaged), ptr(ema_weight), int(mode),
-              ptr(ok), stream())
+              rows.shape[0], ptr(class_steps), n_classes, variant, ptr(coef), *avg_args, ptr(ok), stream())
         return
     _call("mmfn_adamw_rows_f32", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(row_of), ptr(hyper), n_groups, rows.data_ptr(), rows.shape[0],
-          ptr(class_steps), n_classes, variant, ptr(coef), ptr(a), ptr(n_averaged), ptr(ema_weight), int(mode), ptr(ok), stream())
-
-
-def _check_momentum_buffer(buf, p, n):
-    if buf is None or buf.dtype != torch.float32 or buf.device != p.device or buf.numel() < n:
-        raise ValueError("buf (momentum_buffer) is a float32 tensor on the parameters' device with one entry per parameter of the range")
+          ptr(class_steps), n_classes, variant, ptr(coef), *avg_args, ptr(ok), stream())
 
 
 def sgd_groups(p, g, buf, step, hyper, n_groups, group_of=None, n=None, coef=None, avg=None, ok=None, mask=False):
@@ -1285,18 +1300,11 @@ def sgd_groups(p, g, buf, step, hyper, n_groups, group_of=None, n=None, coef=Non
     mask as in adamw_groups."""
     n = p.numel() if n is None else n
     _check_momentum_buffer(buf, p, n)
-    if mask and (group_of is None or group_of.dtype != torch.uint8 or group_of.numel() * 4 < n):
-        raise ValueError("the masked SGD launch needs a uint8 group table with one byte per float4 of the range")
-    a, n_averaged, ema_weight, mode = (None, None, None, 0) if avg is None else avg
-    if a is not None and a.numel() < n:
-        raise ValueError("average holds %d floats, the step covers %d" % (a.numel(), n))
-    if ok is not None and coef is None:
-        raise ValueError("the guarded SGD launch is the coefficient instance: pass coef")
-    variant = sum(bit for bit, arg in ((ADAMW_COEF, coef), (ADAMW_AVG, avg), (ADAMW_GUARD, ok)) if arg is not None)
     if mask:
-        variant |= ADAMW_MASK
-    _call("mmfn_sgd_groups_f32", ptr(p), ptr(g), ptr(buf), n, ptr(group_of), ptr(hyper), n_groups, ptr(step), variant, ptr(coef),
-          ptr(a), ptr(n_averaged), ptr(ema_weight), int(mode), ptr(ok), stream())
+        _check_group_table("SGD", group_of, n)
+    avg_args = _avg_args(avg, n)
+    _call("mmfn_sgd_groups_f32", ptr(p), ptr(g), ptr(buf), n, ptr(group_of), ptr(hyper), n_groups, ptr(step),
+          _step_variant("SGD", coef, avg, ok, mask), ptr(coef), *avg_args, ptr(ok), stream())
 
 
 def sgd_rows(p, g, buf, class_steps, n_classes, hyper, n_groups, row_of, rows, n=None, coef=None, avg=None, ok=None):
@@ -1304,22 +1312,11 @@ def sgd_rows(p, g, buf, class_steps, n_classes, hyper, n_groups, row_of, rows, n
     the row's tensors.  row_of / rows / class_steps as in adamw_rows; coef / avg / ok as in sgd_groups."""
     n = p.numel() if n is None else n
     _check_momentum_buffer(buf, p, n)
-    if row_of is None or row_of.dtype != torch.uint8 or row_of.numel() * 4 < n:
-        raise ValueError("the SGD launch with step classes needs a uint8 row table with one byte per float4 of the range")
-    if rows.device.type != "cpu" or rows.dtype != torch.int32 or rows.dim() != 2 or rows.shape[1] != 2 or not rows.is_contiguous():
-        raise ValueError("rows is a contiguous CPU int32 tensor [n_rows, 2] of (group, class)")
-    if not 1 <= rows.shape[0] <= ADAMW_MAX_ROWS:
-        raise ValueError("%d (group, step class) rows: the SGD launch holds at most %d" % (rows.shape[0], ADAMW_MAX_ROWS))
-    if class_steps.dtype != torch.int64 or class_steps.numel() < n_classes:
-        raise ValueError("class_steps holds %d %s counters, the launch reads %d int64" % (class_steps.numel(), class_steps.dtype, n_classes))
-    a, n_averaged, ema_weight, mode = (None, None, None, 0) if avg is None else avg
-    if a is not None and a.numel() < n:
-        raise ValueError("average holds %d floats, the step covers %d" % (a.numel(), n))
-    if ok is not None and coef is None:
-        raise ValueError("the guarded SGD launch is the coefficient instance: pass coef")
-    variant = sum(bit for bit, arg in ((ADAMW_COEF, coef), (ADAMW_AVG, avg), (ADAMW_GUARD, ok)) if arg is not None)
+    _check_rows("SGD", row_of, rows, class_steps, n_classes, n)
+    avg_args = _avg_args(avg, n)
     _call("mmfn_sgd_rows_f32", ptr(p), ptr(g), ptr(buf), n, ptr(row_of), ptr(hyper), n_groups, rows.data_ptr(), rows.shape[0],
-          ptr(class_steps), n_classes, variant, ptr(coef), ptr(a), ptr(n_averaged), ptr(ema_weight), int(mode), ptr(ok), stream())
+          ptr(class_steps), n_classes, _step_variant("SGD", coef, avg, ok), ptr(coef), *avg_args, ptr(ok), stream())
+
 
 
 def class_steps_advance(class_steps, active, n_classes, ok=None):

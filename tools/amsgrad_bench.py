@@ -7,7 +7,7 @@
     off      mmfn_adamw_groups_ams_f32 with the flag clear in both groups: the bytes of `plain` through the new kernel
     The cases alternate round by round; times are device events around `iters` back-to-back launches.  Expected from the bytes
     moved: amsgrad / plain = 36 / 28 = 1.29.  Under `rocprofv3 --kernel-trace --stats -- python tools/amsgrad_bench.py --only adamw`
-    the kernels appear as adamw_groups_kernel<...> and adamw_groups_ams_kernel<...>.
+    the kernels appear as optim_step_kernel<AdamwRule, GroupSlots, ...> and optim_step_kernel<AdamwAmsRule, GroupSlots, ...>.
 (2) The `amsgrad-err` lines of tests/test_amsgrad_gpu.py (max deviation of both launches from torch.optim.AdamW in float64), when
     --errors names a pytest log that holds them.
 

@@ -9,7 +9,7 @@
     momentum0 mmfn_sgd_groups_f32 with momentum 0 in both groups: buf is neither loaded nor stored, 12 B per parameter
     The cases alternate round by round; times are device events around `iters` back-to-back launches.  Expected from the bytes
     moved: sgd / adamw = 20 / 28 = 0.71.  Under `rocprofv3 --kernel-trace --stats -- python tools/sgd_bench.py --only launch` the
-    kernels appear as adamw_groups_kernel<...>, sgd_groups_kernel<...> and sgd_rows_kernel<...>.
+    kernels appear as optim_step_kernel<AdamwRule, GroupSlots, ...>, <SgdRule, GroupSlots, ...> and <SgdRule, RowSlots, ...>.
 (2) The B = 32 replayed AdamW step with nothing frozen and no FusedSGD constructed: ms per step, and the entry points one eager step
     calls (name: count).  Run `tools/unfreeze_bench.py --only step` on the parent commit and compare the two "launches" lines:
     they must be identical call for call.
